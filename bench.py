@@ -3,6 +3,17 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--quality Q]
                     [--adaptive 0|1] [--kind uniform|smooth|const|extreme]
+                    [--dump-outputs DIR] [--full]
+
+A plain run measures the headline only: it synthesises the frames, pre-warms the
+clocks, runs the W warmup steps, times the K steps, writes the last timed step's
+coefficient planes if --dump-outputs DIR is given (dump_outputs: .npy, float32, a
+fixed seeded sample of the blocks when they exceed the size budget; the inputs
+depend on the arguments alone, so two builds compare output for output) and prints
+the one JSON line.  Every other leg described below -- round_trip, encode, gather,
+band, the small-frame and legacy legs, the memory ceilings, the CPU baseline and
+the oracle's parity checks -- runs only with --full; without it their keys in the
+line are null.
 
 Metric (BASELINE.json): 8x8 macroblocks/s (DCT+quant) and % of HBM roofline.
 Workload: a stream of 4K 4:2:0 frames (BASELINE configs[2] planes: Y 3840x2160 +
@@ -102,6 +113,17 @@ def parse():
                          "(gather, band, symbol-stream gather): the RCCL code path on a single GPU")
     ap.add_argument("--backend", default="nccl", help="N>1 process group (nccl = RCCL; gloo only to rehearse "
                                                       "several ranks on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg: the memory ceilings, the small-frame and "
+                         "legacy per-block legs, the encoder and round trip legs, the N>1 gather / band legs, the "
+                         "CPU baseline with the oracle's parity checks, and the GPU's identity.  Without it a run "
+                         "sets up, warms up, times the steps, writes --dump-outputs and prints the line (the other "
+                         "legs' keys are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed -- the int16 coefficient "
+                         "planes a caller of the step receives -- as DIR/luma_coef.npy and DIR/chroma_coef.npy "
+                         "(float32, [blocks, 64]; at N>1 each rank writes <name>_rank<r>.npy).  More than "
+                         "DUMP_BUDGET_BYTES of output is cut to a fixed, seeded sample of its blocks (dump_outputs)")
     ap.add_argument("--launch-check", action="store_true",
                     help="rank plumbing only, no GPU: every rank joins a gloo group and rank 0 prints the world it "
                          "formed (tests/test_bench_launch.py)")
@@ -1121,6 +1143,36 @@ def ceilings_leg(args, plan, luma, chroma, coef_y, coef_c, dev, rounds=10, b2b=3
                             for k in cases}}
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: float32 bytes written over all files and ranks (under 64 MB)
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(path, named, rank, world):
+    """--dump-outputs DIR: the timed step's outputs (name -> int16 [blocks, 64] on the
+    device) as DIR/<name>.npy, float32 (exact for int16).  When all of them exceed
+    this rank's share of DUMP_BUDGET_BYTES, each is cut to a sample of whole blocks:
+    sorted block indices drawn without replacement by a generator seeded with
+    DUMP_SAMPLE_SEED, in proportion to the outputs' sizes -- the same blocks for the
+    same shapes in every run and every build, so two dumps compare file by file.
+    Returns what was written, for the line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // max(1, world) // (64 * 4)  # blocks this rank may write
+    total = sum(t.shape[0] for _, t in named)
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    written = {}
+    for name, t in named:
+        n = t.shape[0]
+        k = n if total <= cap else max(1, cap * n // total)
+        if k < n:
+            idx = np.sort(rng.choice(n, size=k, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        fname = name + (f"_rank{rank}" if world > 1 else "") + ".npy"
+        np.save(os.path.join(path, fname), t.to(torch.float32).cpu().numpy())
+        written[fname] = {"blocks": k, "of": n, "dtype": "float32"}
+    return {"dir": path, "files": written}
+
+
 def build_record():
     """Which library this line measured: the sha256 of the loaded libdct_amd.so
     and whether it is the one dct_amd/build.py's manifest (build_info.json:
@@ -1158,6 +1210,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))  # one child process per GPU; this process stays off the GPU
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -1266,10 +1320,15 @@ def main():
     avg_launch_bytes = BYTES_PER_BLOCK * (nblk_y + nblk_c) / launches
     achieved = avg_launch_bytes / avg_launch_s / 1e9
 
+    # the last timed step's outputs, before any leg reuses the buffers (ceilings_leg does)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, [("luma_coef", coef_y), ("chroma_coef", coef_c)], rank, world)
+
     # host copies of one chroma plane and its coefficients: the CPU leg (rank 0)
     # checks them against the oracle
     fwd_check = None
-    if rank == 0:
+    if rank == 0 and args.full and not args.no_cpu:
         nk = (C_W // 8) * (C_H // 8)
         fwd_check = (chroma[0].cpu().numpy(), coef_c[:nk].cpu().numpy())
     trace("headline done")
@@ -1311,7 +1370,15 @@ def main():
         "note": "u8 pixels in, int16 coefficients out; fp32 AAN butterfly with the exact fp64 "
                 "reference-order recomputation for guard-band (tie) coefficients",
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     report.out = out
+    if not args.full:  # a plain run ends here: the headline alone (every other leg is behind --full)
+        out["legs"] = {}
+        report.emit()
+        if dist_on:
+            dist.destroy_process_group()
+        return
     legs = Legs(report, dist_on, args.leg_deadline or 2 * args.dist_timeout + 60.0)
     out["legs"] = legs.status
 

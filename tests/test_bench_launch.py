@@ -237,3 +237,44 @@ def test_merge_methods_and_fault_injection():
     with pytest.raises(RuntimeError, match="injected"):
         bench.inject_p2p_fault(args, 4, 3, "p2p")
     bench.inject_p2p_fault(types.SimpleNamespace(gather_fault="offset", dist_timeout=1.0), 4, 3, "p2p")
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """bench.dump_outputs (--dump-outputs): outputs over the size budget are cut to whole blocks at
+    sorted, distinct indices, in proportion to the outputs' sizes, the same ones in every call;
+    the files are float32, hold the source's values exactly and stay under 64 MB in all; outputs
+    under the budget are written whole; at N>1 a rank writes its share under its own names."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 10**6
+    cap = bench.DUMP_BUDGET_BYTES // 256
+
+    def planes(n):  # block i carries its own index in its first two coefficients
+        t = torch.zeros((n, 64), dtype=torch.int16)
+        i = torch.arange(n)
+        t[:, 0], t[:, 1], t[:, 63] = (i % 30000).to(torch.int16), (i // 30000).to(torch.int16), -7
+        return t
+
+    big, small = planes(cap + 1001), planes((cap + 1001) // 2)
+    runs = []
+    for d in ("a", "b"):
+        rep = bench.dump_outputs(str(tmp_path / d), [("luma_coef", big), ("chroma_coef", small)], 0, 1)
+        assert set(rep["files"]) == {"luma_coef.npy", "chroma_coef.npy"}
+        runs.append({f: np.load(tmp_path / d / f) for f in rep["files"]})
+    total = 0
+    for (f, got), src in zip(runs[0].items(), (big, small)):
+        assert got.dtype == np.float32 and got.shape[1] == 64 and 0 < got.shape[0] < src.shape[0]
+        assert rep["files"][f] == {"blocks": got.shape[0], "of": src.shape[0], "dtype": "float32"}
+        idx = (got[:, 0] + 30000 * got[:, 1]).astype(np.int64)
+        assert np.all(np.diff(idx) > 0) and idx[-1] < src.shape[0]
+        assert np.array_equal(got, src.numpy()[idx].astype(np.float32))
+        assert np.array_equal(got, runs[1][f])
+        total += got.nbytes
+    assert 0.9 * bench.DUMP_BUDGET_BYTES < total <= bench.DUMP_BUDGET_BYTES
+    assert abs(runs[0]["luma_coef.npy"].shape[0] - 2 * runs[0]["chroma_coef.npy"].shape[0]) <= 2
+    rep = bench.dump_outputs(str(tmp_path / "c"), [("luma_coef", small[:1000])], 0, 1)
+    assert np.array_equal(np.load(tmp_path / "c" / "luma_coef.npy"), small[:1000].numpy().astype(np.float32))
+    rep = bench.dump_outputs(str(tmp_path / "d"), [("luma_coef", big)], 1, 2)
+    assert list(rep["files"]) == ["luma_coef_rank1.npy"] and rep["files"]["luma_coef_rank1.npy"]["blocks"] == cap // 2

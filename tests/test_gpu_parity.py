@@ -658,7 +658,7 @@ def test_bench_gpus2_gloo(T, dm):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR",
                                                             "MASTER_PORT")}
     env["DCTQ_BENCH_TRACE"] = "1"
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1",
            "--no-cpu", "--frames", "2", "--total-frames", "4", "--gather-steps", "2", "--round-trip-steps", "1",
            "--encode-steps", "1", "--ceiling-rounds", "0", "--prewarm-ms", "0"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
@@ -721,7 +721,7 @@ def test_dist_legs_rccl_one_rank(T, dm):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, "bench.py", "--dist-legs", "--steps", "2", "--warmup", "1", "--no-cpu", "--frames", "2",
+    cmd = [sys.executable, "bench.py", "--full", "--dist-legs", "--steps", "2", "--warmup", "1", "--no-cpu", "--frames", "2",
            "--total-frames", "2", "--gather-steps", "2", "--round-trip-steps", "0", "--encode-steps", "1",
            "--ceiling-rounds", "0", "--prewarm-ms", "0"]
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=240)
@@ -750,7 +750,7 @@ def test_bench_json_contract(T, dm):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--frames", "2", "--cpu-seconds", "2",
+    cmd = [sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--frames", "2", "--cpu-seconds", "2",
            "--ceiling-rounds", "1", "--round-trip-steps", "1", "--encode-steps", "1", "--prewarm-ms", "20"]
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, _tail(r.stderr)
@@ -777,6 +777,44 @@ def test_bench_json_contract(T, dm):
     assert rt["parity_check"] is True, rt.get("parity")
     mc = rt["movement_ceiling"]
     assert 0 < mc["fused_frac"] < 1 and 0 < mc["movement_frac"] < 1 and 0 < mc["flat_124_frac"] < 1, mc
+
+
+def test_bench_plain_run_and_dump_outputs(T, dm, tmp_path):
+    """bench.py without --full measures the headline only (every other leg's key is null,
+    no leg ran), --steps is the number of timed steps that ms_per_step averages over, and
+    --dump-outputs writes the last timed step's coefficient planes: float32 .npy files that
+    equal a forward of the same seeded frames in this process, block for block (one frame:
+    under the size budget, so every block is written)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", "1",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, _tail(r.stderr)
+    lines = [x for x in r.stdout.splitlines() if x.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["higher_is_better"] is True
+    assert d["unit"] == "macroblocks/s" and d["dtype"] == "fp32" and d["metric"].startswith("8x8 macroblocks/sec")
+    nblk = d["config"]["blocks_per_gpu_step"]
+    assert nblk == 194400 and d["ms_per_step"] > 0
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - nblk) < 1e-3 * d["value"]
+    assert 0 < d["roofline"]["frac"] < 1 and d["roofline"]["movement_ceiling"] is None
+    for k in ("cpu_baseline", "parity_check", "gather", "band", "round_trip", "encode", "small_frame",
+              "legacy_per_block", "gpu"):
+        assert d[k] is None, k
+    assert d["legs"] == {}
+    assert sorted(os.listdir(tmp_path)) == ["chroma_coef.npy", "luma_coef.npy"]
+    luma = dm.synth(12345, "uniform", 3840, 2160, 1)
+    chroma = dm.synth(12345 + 50000, "uniform", 1920, 1080, 2)
+    want = dm.Plan(50, 0).forward_quant_planes([luma, chroma])
+    for name, w in zip(("luma_coef", "chroma_coef"), want):
+        got = np.load(tmp_path / (name + ".npy"))
+        assert got.dtype == np.float32 and got.shape == tuple(w.shape), (name, got.dtype, got.shape)
+        assert d["dump_outputs"]["files"][name + ".npy"]["blocks"] == w.shape[0]
+        assert np.array_equal(got, w.cpu().numpy().astype(np.float32)), name
 
 
 def test_diag_stream_moves_bytes(T, dm):

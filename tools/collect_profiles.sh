@@ -5,7 +5,7 @@
 #   1. separate --pmc FETCH_SIZE / WRITE_SIZE passes over bench.py -> traffic.json
 #      (configuration + library hash recorded: bench.py uses it only for a matching run)
 #   2. rocprofv3 --kernel-trace --stats over the bench command (with its clock pre-warm)
-#   3. bench.py (the driver's command), which picks traffic.json up
+#   3. bench.py --full (the headline and every other leg), which picks traffic.json up
 #   4. kernel stats of the round trip, RLE and Huffman kernels (tools/rt_bench.py, aux_bench.py)
 #   5. the forward kernel over every input kind x plan beside its movement (tools/perf_matrix.py)
 #      and the Huffman sizes per input kind (tools/huf_ab.py)
@@ -23,7 +23,7 @@ echo "traffic done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- \
   python bench.py --steps 10 --warmup 3 --no-cpu --round-trip-steps 0 --encode-steps 0 --ceiling-rounds 0 > $O/prof_bench.log 2>&1
 echo "prof done"
-timeout -k 10 600 python bench.py > $O/bench.log 2>&1
+timeout -k 10 600 python bench.py --full > $O/bench.log 2>&1
 echo "bench done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_rt -o run --output-format csv -- \
   python tools/rt_bench.py 64 > $O/rt_bench.log 2>&1

@@ -24,7 +24,7 @@ echo "traffic ok" &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- \
   python bench.py --steps 10 --warmup 3 --no-cpu --round-trip-steps 0 --encode-steps 0 --ceiling-rounds 0 > $O/prof_bench.log 2>&1 &&
 echo "prof ok" &&
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err &&
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err &&
 echo "bench ok" &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_rt -o run --output-format csv -- \
   python tools/rt_bench.py 64 > $O/rt_bench.log 2>&1 &&
