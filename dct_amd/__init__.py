@@ -50,6 +50,7 @@ def _bind(L: C.CDLL, diagnostic: bool) -> C.CDLL:
         "dctq_abi_version": ([], i),
         "dctq_forward_float": ([vp, C.POINTER(_Plane), vp, vp], i),
         "dctq_inverse": ([vp, vp, vp, ll, vp, vp], i),
+        "dctq_decode_planes": ([vp, vp, vp, C.POINTER(_Plane), i, vp], i),
         "dctq_synth": ([C.c_uint64, i, C.POINTER(_Plane), vp], i),
         "dctq_error_string": ([i], C.c_char_p),
         "dctq_synchronize": ([vp], i),
@@ -392,12 +393,57 @@ class Plan:
                      n, C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
         return out
 
+    def decode_planes(self, coefs, shapes=None, outs=None, var_nums=None, stream=None):
+        """Quantized coefficients -> u8 pixels of up to 4 planes in ONE launch
+        (dctq_decode_planes): coefs[k] int16 [nblk_k, 64] in forward_quant's block order,
+        var_nums[k] int32 [nblk_k] (required for adaptive plans, ignored otherwise).
+        shapes[k] is (F, H, W) or (H, W); outs[k], if given, is a u8 tensor [F, H, W] or
+        [H, W] and may be a strided view (e.g. a padded buffer sliced to width): bytes
+        outside width x height of each frame are not touched.  One of shapes / outs is
+        needed.  Returns the list of u8 tensors [F, H, W] (outs as given), each pixel
+        rne(clamp(r, 0, 255)) of the fp32 recon r that round_trip_planes reports."""
+        import torch
+        n = len(coefs)
+        if shapes is None and outs is None:
+            raise DctqError("decode_planes needs shapes or outs")
+        for name, ts in (("shapes", shapes), ("outs", outs), ("var_nums", var_nums)):
+            if ts is not None and len(ts) != n:
+                raise DctqError(f"{name} needs one entry per plane ({n}), got {len(ts)}")
+        if shapes is not None:
+            shapes = [(1, *map(int, s)) if len(s) == 2 else tuple(map(int, s)) for s in shapes]
+            if any(len(s) != 3 for s in shapes):
+                raise DctqError("shapes entries must be (F, H, W) or (H, W)")
+        if outs is None:
+            outs = [torch.empty(s, dtype=torch.uint8, device=c.device) for s, c in zip(shapes, coefs)]
+        descs = (_Plane * n)(*[plane_desc(o) for o in outs])
+        nbs = [d.nframes * (d.width // 8) * (d.height // 8) for d in descs]
+        for k, (d, o, c) in enumerate(zip(descs, outs, coefs)):
+            if shapes is not None and (d.nframes, d.height, d.width) != shapes[k]:
+                raise DctqError(f"outs[{k}] is {tuple(o.shape)}, shapes[{k}] says {shapes[k]}")
+            if d.width % 8 or d.height % 8:
+                raise DctqError(f"outs[{k}]: width and height must be multiples of 8")
+            _need(c, nbs[k] * 64, torch.int16, f"coefs[{k}]", o.device)
+            if var_nums is not None:
+                _need(var_nums[k], nbs[k], torch.int32, f"var_nums[{k}]", o.device)
+        cp = (C.c_void_p * n)(*[c.data_ptr() for c in coefs])
+        vp = (C.c_void_p * n)(*[v.data_ptr() for v in var_nums]) if var_nums is not None else None
+        self._chk(self._L.dctq_decode_planes(self._h, C.cast(cp, C.c_void_p),
+                                             C.cast(vp, C.c_void_p) if vp is not None else None, descs, n,
+                                             _stream_ptr(stream)))
+        return outs
+
+    def decode(self, coef, shape=None, out=None, var_num=None, stream=None):
+        """One plane of decode_planes: int16 [nblk, 64] -> u8 [F, H, W]."""
+        return self.decode_planes([coef], None if shape is None else [shape], None if out is None else [out],
+                                  None if var_num is None else [var_num], stream)[0]
+
 
 def stream_release(stream=None, diagnostic: bool = False) -> None:
-    """diagnostic=True: dctq_diag_stream_release -- wait for `stream` (torch's current
-    one by default) and free the tie-path stashes this thread's v2 (variant 4)
-    launches on it hold.  The product's dctq_stream_release is a no-op (it keeps no
-    per-stream memory)."""
+    """The calling thread forgets `stream` (torch's current one by default) in the
+    library's launch-isolation list (dctq_stream_release; call it before destroying the
+    stream).  The product keeps no per-stream memory.  diagnostic=True:
+    dctq_diag_stream_release -- wait for the stream and free the tie-path stashes
+    this thread's v2 (variant 4) launches on it hold."""
     L = diag() if diagnostic else lib()
     fn = L.dctq_diag_stream_release if diagnostic else L.dctq_stream_release
     _check(fn(_stream_ptr(stream)), L)

@@ -537,6 +537,32 @@ int dctq_inverse(const dctq_plan *plan, const int16_t *coef, const int32_t *var_
     return DCTQ_OK;
 }
 
+int dctq_decode_planes(const dctq_plan *plan, const int16_t *const *coef, const int32_t *const *var_num,
+                       const dctq_plane *dst, int nplanes, void *stream) {
+    DCTQ_LAUNCH(stream, 14);
+    if (int rc = dctq::check_plan(plan)) return rc;
+    if (!coef || !dst) return fail(DCTQ_EINVAL, "coef/dst is NULL");
+    if (nplanes < 1 || nplanes > dctq::kMaxPlanes) return fail(DCTQ_EINVAL, "nplanes must be in [1, 4]");
+    if (plan->adaptive && !var_num) return fail(DCTQ_EINVAL, "adaptive decode needs var_num");
+    dctq::DecodeSet ds = {};
+    ds.n = nplanes;
+    uint32_t first = 0;
+    for (int k = 0; k < nplanes; ++k) {
+        if (int rc = dctq::plane_args(&dst[k], &ds.pl[k])) return rc;
+        if (!coef[k]) return fail(DCTQ_EINVAL, "coef[k] is NULL");
+        if (((uintptr_t)coef[k]) % 16) return fail(DCTQ_EINVAL, "coef must be 16-byte aligned");
+        if (plan->adaptive && !var_num[k]) return fail(DCTQ_EINVAL, "adaptive decode needs every var_num[k]");
+        ds.coef[k] = coef[k];
+        ds.var[k] = plan->adaptive ? var_num[k] : nullptr;
+        ds.first[k] = first;
+        first += (uint32_t)((ds.pl[k].nblk + 31) / 32);  // < 4 * 2^26
+    }
+    for (int k = nplanes; k <= dctq::kMaxPlanes; ++k) ds.first[k] = first;
+    HIPCHK(dctq::launch_decode(ds, plan->dev, plan->adaptive, plan->inv_f32 != 0, (hipStream_t)stream, plan->num_cus),
+           "decode launch");
+    return DCTQ_OK;
+}
+
 int dctq_synth(uint64_t seed, int kind, const dctq_plane *dst, void *stream) {
     DCTQ_LAUNCH(stream, 5);
     if (!dst || !dst->pixels) return fail(DCTQ_EINVAL, "dst is NULL");

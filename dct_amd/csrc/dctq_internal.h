@@ -149,6 +149,16 @@ struct RoundTripSet {
     float *recon[kMaxPlanes];
 };
 
+// The pixel decoder's planes (decode.hip): pl[k].src is the DESTINATION plane, written
+// through; coefficients (and var_num, adaptive plans) in, block-major.
+struct DecodeSet {
+    PlaneArgs pl[kMaxPlanes];
+    const int16_t *coef[kMaxPlanes];
+    const int32_t *var[kMaxPlanes];    // adaptive plans: all set; otherwise unused
+    uint32_t first[kMaxPlanes + 1];    // global index of each plane's first 32-block batch; first[n..] = total
+    int n;
+};
+
 // The product forward (fdct8.hip): fdct8_quant_v3 over every plane of ps, every plan.
 hipError_t launch_fdct8_quant(const PlaneSet &ps, const DevTables *dev, int adaptive, unsigned long long *fallbacks,
                               hipStream_t stream, int num_cus);
@@ -162,6 +172,9 @@ hipError_t launch_fdct8_movement(const PlaneSet &ps, const DevTables *dev, hipSt
                                  int grid_mult = 0);
 hipError_t launch_roundtrip(const RoundTripSet &rt, const DevTables *dev, int adaptive, bool inv_f32,
                             unsigned long long *fallbacks, hipStream_t stream, int num_cus);
+// dequantize + inverse DCT + 128 + clamp to u8 pixels in the planes of ds (decode.hip)
+hipError_t launch_decode(const DecodeSet &ds, const DevTables *dev, int adaptive, bool inv_f32, hipStream_t stream,
+                         int num_cus);
 // diagnostic: roundtrip8_f32's data movement without arithmetic (fdct8_diag.hip)
 hipError_t launch_roundtrip_movement(const RoundTripSet &rt, hipStream_t stream, int num_cus);
 size_t encode_workspace_bytes(long long nbatch);

@@ -1,0 +1,155 @@
+// dct_amd/csrc/decode.hip -- dctq_decode_planes: quantized coefficients -> u8 pixels,
+// for every block of up to 4 planes in ONE launch,
+//   pix = (uint8) rne(min(max(r, 0), 255)),  r = fp32(dct_inverse(dequantize(coef)) + 128)
+// with r exactly the value the fused round trip stores as recon for the same plan
+// (inverse_core.h: inverse_half_f32 for plans the fp32 bound admits, the fp64
+// inverse_half<ADAPTIVE> rounded once to fp32 otherwise), i.e. the last arrow of the
+// reference's pipeline tests/test_entropy.c:350-393 (dequantize, dct_inverse, clamp).
+//
+// 128 B in + 64 B out per block (+ 4 B of var_num, adaptive plans) against the 384 B
+// of dctq_inverse, whose fp32 block-major recon a host then has to clamp and un-tile.
+//
+// Paired-lane layout of idct8_pair (f64_pair.hip): one wave, one 32-block batch, lane
+// (h, j) = rows 4h..4h+3 of block j.  Persistent grid-stride loop over the global
+// batch numbering of all planes; the next batch's four 16 B coefficient rows (and
+// var_num) are prefetched into registers with non-temporal loads.  The lane's four
+// rows are clamped, rounded and packed to 8 B each in registers and stored straight
+// to their image position: lanes j, j+1, ... of one block row are contiguous, so a
+// wave writes runs of up to 256 B per image row.  No LDS, so the store-data hazard
+// of DESIGN.md does not arise.  The stores are non-temporal and go through a buffer
+// descriptor over the plane (PlaneArgs::span bytes from its first pixel): an address
+// that went wrong drops the write instead of faulting, as load_rows<true> does for
+// reads.  Lanes past the plane's last block store nothing.
+#include "inverse_core.h"
+
+namespace dctq {
+
+// The grid of launch_persistent (f64_pair.hip): up to 64 x the resident workgroups.
+constexpr int kDecodeGridMult = 64;
+
+__device__ __forceinline__ const int16_t *coef_in(const DecodeSet &ds, int k) {
+    const int16_t *c = ds.coef[0];
+#pragma unroll
+    for (int i = 1; i < kMaxPlanes; ++i) c = k == i ? ds.coef[i] : c;
+    return c;
+}
+__device__ __forceinline__ const int32_t *var_in(const DecodeSet &ds, int k) {
+    const int32_t *v = ds.var[0];
+#pragma unroll
+    for (int i = 1; i < kMaxPlanes; ++i) v = k == i ? ds.var[i] : v;
+    return v;
+}
+// First global batch of plane k / plane of global batch g (both wave-uniform), as
+// first_of / plane_of of fdct8_core.h over 32-block batches.
+__device__ __forceinline__ uint32_t first_batch(const DecodeSet &ds, int k) {
+    uint32_t f = 0u;
+#pragma unroll
+    for (int i = 1; i < kMaxPlanes; ++i) f = k == i ? ds.first[i] : f;
+    return f;
+}
+__device__ __forceinline__ int plane_of_batch(const DecodeSet &ds, uint32_t g) {
+    int k = 0;
+#pragma unroll
+    for (int i = 1; i < kMaxPlanes; ++i) k += (i < ds.n && g >= ds.first[i]) ? 1 : 0;
+    return k;
+}
+
+// Coefficient rows 4h..4h+3 (16 B each) of block j of global batch g, and its variance
+// numerator; read once, so non-temporal.  Past the plane's end (and past the last
+// batch, for the final prefetch): block 0 of the last plane.
+template <bool ADAPTIVE>
+__device__ __forceinline__ void prefetch_coefs(const DecodeSet &ds, uint32_t g, int h, int j, uint4 (&rows)[4],
+                                               int32_t &vn) {
+    const int k = plane_of_batch(ds, g);
+    const uint32_t n = (g - first_batch(ds, k)) * 32u + (uint32_t)j;
+    const uint32_t m = n < (uint32_t)ds.pl[k].nblk ? n : 0u;
+    const u4p *src = reinterpret_cast<const u4p *>(coef_in(ds, k) + (size_t)m * 64) + 4 * h;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const u4p t = __builtin_nontemporal_load(src + r);
+        rows[r] = make_uint4(t.x, t.y, t.z, t.w);
+    }
+    if (ADAPTIVE) vn = __builtin_nontemporal_load(var_in(ds, k) + m);
+}
+
+// Four fp32 pixels -> 4 bytes: clamp to [0, 255] (v_med3_f32), round to nearest even
+// (v_rndne_f32), then the conversion of an exact integer (v_cvt_pk_u8_f32 inserts byte
+// k of the word).
+__device__ __forceinline__ uint32_t pack_u8x4(float a, float b, float c, float d) {
+    uint32_t w = 0u;
+    w = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_rintf(__builtin_amdgcn_fmed3f(a, 0.0f, 255.0f)), 0u, w);
+    w = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_rintf(__builtin_amdgcn_fmed3f(b, 0.0f, 255.0f)), 1u, w);
+    w = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_rintf(__builtin_amdgcn_fmed3f(c, 0.0f, 255.0f)), 2u, w);
+    w = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_rintf(__builtin_amdgcn_fmed3f(d, 0.0f, 255.0f)), 3u, w);
+    return w;
+}
+
+template <bool ADAPTIVE, bool INV32>
+__global__ __launch_bounds__(kThreadsP, 4) void decode8(DecodeSet ds, const DevTables *__restrict__ dev) {
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int h = lane >> 5, j = lane & 31;
+    const uint32_t nbatch = ds.first[kMaxPlanes];
+    const uint32_t step = gridDim.x * kWavesP;
+    uint32_t g = blockIdx.x * kWavesP + wv;
+    uint4 nxt[4];
+    int32_t nvn = 0;
+    prefetch_coefs<ADAPTIVE>(ds, g, h, j, nxt, nvn);
+    for (; g < nbatch; g += step) {
+        const int k = plane_of_batch(ds, g);
+        const PlaneArgs &p = ds.pl[k];
+        const uint32_t n = (g - first_batch(ds, k)) * 32u + (uint32_t)j;
+        const bool valid = n < (uint32_t)p.nblk;
+        uint4 cur[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) cur[r] = nxt[r];
+        const int32_t vn = nvn;
+        prefetch_coefs<ADAPTIVE>(ds, g + step, h, j, nxt, nvn);
+
+        // the whole wave runs the arithmetic (exec-masked scales and lane-half swaps inside)
+        u2p pix[4];
+        const auto pack = [&pix](int r, int c, const float (&o)[4]) { pix[r][c >> 2] = pack_u8x4(o[0], o[1], o[2], o[3]); };
+        if constexpr (INV32) inverse_half_f32_rows(dev, cur, h, pack);
+        else inverse_half_rows<ADAPTIVE>(dev, cur, vn, h, pack);
+
+        // image position of rows 4h..4h+3 of block n (frame, block row, block column)
+        const uint32_t m = valid ? n : 0u;
+        const uint32_t f = fdiv(m, p.div_frame);
+        const uint32_t rem = m - f * (uint32_t)p.nblk_frame;
+        const uint32_t by = fdiv(rem, p.div_bw);
+        const uint32_t bx = rem - by * (uint32_t)p.bw;
+        uint8_t *base = const_cast<uint8_t *>(p.src);
+        if (p.span) {  // kernel argument: wave-uniform.  Every offset inside the plane is < 2^32
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, (int)p.span, 0x00020000);
+            const uint32_t st = (uint32_t)p.stride;
+            const uint32_t off = f * (uint32_t)p.frame_stride + (by * 8u + 4u * (uint32_t)h) * st + bx * 8u;
+            if (valid) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) __builtin_amdgcn_raw_buffer_store_b64(pix[r], rs, off + r * st, 0, kNtAux);
+            }
+        } else if (valid) {  // a plane of 4 GiB or more: 64-bit addresses
+            uint8_t *px = base + (long long)f * p.frame_stride + (long long)(by * 8u + 4u * (uint32_t)h) * p.stride +
+                          (long long)bx * 8;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) __builtin_nontemporal_store(pix[r], reinterpret_cast<u2p *>(px + r * p.stride));
+        }
+    }
+}
+
+template <bool A, bool F32>
+static hipError_t launch_dec(const DecodeSet &ds, const DevTables *dev, hipStream_t stream, int num_cus) {
+    static const int per_cu = resident_per_cu(decode8<A, F32>, kThreadsP);
+    const uint32_t nbatch = ds.first[kMaxPlanes];
+    const uint32_t want = (nbatch + kWavesP - 1) / kWavesP;
+    const uint32_t cap = (uint32_t)(num_cus * per_cu * kDecodeGridMult);
+    hipLaunchKernelGGL((decode8<A, F32>), dim3(want < cap ? want : cap), dim3(kThreadsP), 0, stream, ds, dev);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode(const DecodeSet &ds, const DevTables *dev, int adaptive, bool inv_f32, hipStream_t stream,
+                         int num_cus) {
+    if (adaptive) return launch_dec<true, false>(ds, dev, stream, num_cus);
+    if (inv_f32) return launch_dec<false, true>(ds, dev, stream, num_cus);
+    return launch_dec<false, false>(ds, dev, stream, num_cus);
+}
+
+}  // namespace dctq

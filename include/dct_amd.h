@@ -143,6 +143,28 @@ int dctq_forward_float(const dctq_plan *plan, const dctq_plane *src, float *coef
 int dctq_inverse(const dctq_plan *plan, const int16_t *coef, const int32_t *var_num, long long nblocks,
                  float *recon, void *stream);
 
+/* Decoder: quantized coefficients -> u8 pixels (the reference's decode loop
+ * tests/test_entropy.c:350-393: dequantize -> dct_inverse -> + 128 -> clamp), for
+ * up to 4 planes of independent geometry in ONE launch.  For plane k and block b
+ * in raster order (frame, block row, block column: the order dctq_forward_quant
+ * writes), the 8x8 pixels of coef[k][b][64] go to their image position in dst[k]
+ * (stride and frame_stride honoured; dst[k].pixels is written through, as
+ * dctq_synth does).  Bytes outside width x height of each frame -- row padding,
+ * gaps between frames -- are not touched.
+ *   pix = (uint8_t) rne(min(max(r, 0), 255)),  rne = round to nearest, ties to even,
+ * where r is the fp32 value dctq_round_trip_planes stores as recon for the same
+ * plan and coefficients (so the result equals clamping and rounding that recon,
+ * bit for bit); hence |pix - clamp(dct_inverse(dequantize(coef)) + 128, 0, 255)|
+ * <= 0.5 + 1e-4 for every pixel.
+ * var_num[k] (per block, as dctq_forward_quant writes it) is required for
+ * adaptive plans; non-adaptive plans ignore var_num, which may be NULL.
+ * coef[k] 16-byte aligned; dst[k] as every dctq_plane (pixels 8-byte aligned,
+ * stride a multiple of 8 and >= width, width and height multiples of 8).
+ * 128 B read + 64 B written per block (+ 4 B adaptive), against 384 B for
+ * dctq_inverse and a host-side clamp and un-tiling.  Allocates nothing. */
+int dctq_decode_planes(const dctq_plan *plan, const int16_t *const *coef, const int32_t *const *var_num,
+                       const dctq_plane *dst, int nplanes, void *stream);
+
 /* Zigzag + run-length symbols of quantized blocks (the reference's
  * run_length_encode, src/entropy.c:216-256 over block_to_zigzag :158-178, for
  * every block, blocks concatenated in order).  symbol = (uint16_t)value |
