@@ -522,7 +522,7 @@ def forward_kernel(quality: int, adaptive: bool, batches: int, num_cus: int) -> 
 def inverse_bound(quality: int, adaptive: bool = False):
     """Host-only: (bound, admitted) -- the rigorous bound of |recon - reference| of the
     fused round trip's fp32 inverse for this standard-table plan, and whether
-    round_trip_planes runs that inverse for it (tools/inv_bound.py, api.hip)."""
+    round_trip_planes runs that inverse for it (tools/inv_bound.py, plan_tables.hip)."""
     a = C.c_int(0)
     b = diag().dctq_debug_inverse_bound(int(quality), int(bool(adaptive)), C.byref(a))
     return float(b), bool(a.value)

@@ -110,7 +110,7 @@ int dctq_debug_tables(int quality, int adaptive, float *w, float *thr, double *d
 int dctq_debug_dc_table(int quality, int16_t *out);
 int dctq_debug_fastdiv(uint32_t d, uint32_t n);
 /* The rigorous bound of |recon - reference| of the round trip's fp32 inverse for a
- * standard-table plan (api.hip inverse_f32_bound); *admitted = whether
+ * standard-table plan (plan_tables.hip inverse_f32_bound); *admitted = whether
  * dctq_round_trip_planes runs that inverse for it (non-adaptive, bound <= 5e-5). */
 double dctq_debug_inverse_bound(int quality, int adaptive, int *admitted);
 /* The encoder's symbol bytes (2 or 4) for a standard-table plan (dctq_plan_symbol_bytes). */

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <optional>
+#include <type_traits>
 
 namespace dctq {
 
@@ -36,10 +37,28 @@ class RandIsolation {
 // an entry point on a stream, so that call is isolated as above; every later call
 // of the thread with the same (device, stream, entry point) takes no lock and
 // touches no global state (the reference API is reentrant and keeps
-// no mutable global state).  `entry` < 32 names the entry point.
+// no mutable global state).  `entry` names the entry point: one bit of a 32-bit mask each.
+enum Entry : int {
+    kEntryForwardQuantPlanes,
+    kEntryRoundTripPlanes,
+    kEntryEncodePlanes,
+    kEntryEncodePlanes16,
+    kEntryForwardFloat,
+    kEntryInverse,
+    kEntryDecodePlanes,
+    kEntrySynth,
+    kEntryRleCount,
+    kEntryRleEmit,
+    kEntryRleDecode,
+    kEntryRleDecode16,
+    kEntryHuffmanBits,
+    kEntryHuffmanBitsPlanes,
+    kEntrySynchronize,
+};
+static_assert(kEntrySynchronize < 32, "LaunchIsolation keeps one bit per entry point in a uint32_t");
 class LaunchIsolation {
   public:
-    LaunchIsolation(const void *stream, int entry);
+    LaunchIsolation(const void *stream, Entry entry);
     LaunchIsolation(const LaunchIsolation &) = delete;
     LaunchIsolation &operator=(const LaunchIsolation &) = delete;
 
@@ -59,14 +78,44 @@ void forget_stream(const void *stream);
 void legacy_lane_counts(int *made, int *pooled);
 
 
-// Resident workgroups per CU of `kernel` at `threads` per workgroup (>= 1).  The
-// launchers cache it in a function-local static (thread-safe initialisation):
-// every device this library runs on is a gfx950.
+// Resident workgroups per CU of `kernel` at `threads` per workgroup (>= 1).
 template <typename K>
 inline int resident_per_cu(K kernel, int threads) {
     int nb = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, 0) != hipSuccess || nb < 1) nb = 1;
     return nb;
+}
+
+// The grid of a persistent grid-stride kernel over `nbatch` batches, one per wave and
+// step: a workgroup per `Waves` batches, at most `mult` x the resident workgroups.
+// The occupancy is cached per kernel (the kernel is a template argument, so every
+// instantiation has its own static; thread-safe initialisation): every device this
+// library runs on is a gfx950.
+template <auto Kernel, int Threads, int Waves>
+inline uint32_t persistent_grid(uint64_t nbatch, int num_cus, int mult) {
+    static const int per_cu = resident_per_cu(Kernel, Threads);
+    const uint64_t want = (nbatch + Waves - 1) / Waves;
+    const uint64_t cap = (uint64_t)num_cus * per_cu * mult;
+    return (uint32_t)(want < cap ? want : cap);
+}
+// ... and its launch; Mult is the kernel's own grid multiplier (kGridMult below).
+template <auto Kernel, int Threads, int Waves, int Mult, typename... A>
+inline hipError_t launch_persistent(uint64_t nbatch, int num_cus, hipStream_t stream, A... args) {
+    hipLaunchKernelGGL(Kernel, dim3(persistent_grid<Kernel, Threads, Waves>(nbatch, num_cus, Mult)), dim3(Threads), 0,
+                       stream, args...);
+    return hipGetLastError();
+}
+
+// f(std::bool_constant<b0>(), std::bool_constant<b1>(), ...): run-time flags into the
+// template arguments of a kernel, one leaf per combination.
+template <typename F>
+inline auto with_bools(F &&f) {
+    return f();
+}
+template <typename F, typename... B>
+inline auto with_bools(F &&f, bool b0, B... rest) {
+    return with_bools(
+        [&](auto... c) { return b0 ? f(std::true_type(), c...) : f(std::false_type(), c...); }, rest...);
 }
 
 // Persistent grid-stride kernels launch kGridMult times their resident
@@ -80,6 +129,14 @@ constexpr int kGridMult = 8;
 // (buffer-store aux bits, gfx950: 1 sc0, 2 nt, 16 sc1).  Non-temporal: the
 // written lines are never re-read by the kernel that writes them.
 constexpr int kNtAux = 2;
+// Word 3 of every buffer descriptor here: DATA_FORMAT 32 (bit 17) and nothing else --
+// a raw buffer, byte offsets, accesses at or past num_records dropped (loads read 0).
+constexpr int kRsrcFlags = 0x00020000;
+// s_waitcnt vmcnt(0): the wave's loads have arrived and its stores have read their
+// data VGPRs (and left the CU).
+__device__ __forceinline__ void retire_stores() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+// s_waitcnt lgkmcnt(0): the wave's LDS (and scalar) accesses are done.
+__device__ __forceinline__ void lgkm_wait() { __builtin_amdgcn_s_waitcnt(0xC07F); }
 
 // n / d and n % d by multiply-high, valid for 0 <= n < 2^31 (host-built magic).
 struct FastDiv {
@@ -158,6 +215,42 @@ struct DecodeSet {
     uint32_t first[kMaxPlanes + 1];    // global index of each plane's first 32-block batch; first[n..] = total
     int n;
 };
+
+// Plane selection over a PlaneSet or a DecodeSet (64- or 32-block batches).
+// Coefficient / var_num pointer of plane k (wave-uniform or not: a select chain, no
+// indexed kernel-argument loads).
+template <typename Set>
+__device__ __forceinline__ auto coef_of(const Set &ps, uint32_t k) {
+    auto c = ps.coef[0];
+#pragma unroll
+    for (int i = 1; i < kMaxPlanes; ++i) c = k == (uint32_t)i ? ps.coef[i] : c;
+    return c;
+}
+template <typename Set>
+__device__ __forceinline__ auto var_of(const Set &ps, uint32_t k) {
+    auto v = ps.var[0];
+#pragma unroll
+    for (int i = 1; i < kMaxPlanes; ++i) v = k == (uint32_t)i ? ps.var[i] : v;
+    return v;
+}
+// First global batch of plane k (wave-uniform k): a select chain over the batch
+// prefixes, which sit in SGPRs for the whole kernel -- an indexed kernel-argument
+// load here was one more scalar-cache round trip in front of every prefetch.
+template <typename Set>
+__device__ __forceinline__ uint32_t first_of(const Set &ps, int k) {
+    uint32_t f = 0u;
+#pragma unroll
+    for (int i = 1; i < kMaxPlanes; ++i) f = k == i ? ps.first[i] : f;
+    return f;
+}
+// Plane of global batch g (wave-uniform).
+template <typename Set>
+__device__ __forceinline__ int plane_of(const Set &ps, uint32_t g) {
+    int k = 0;
+#pragma unroll
+    for (int i = 1; i < kMaxPlanes; ++i) k += (i < ps.n && g >= ps.first[i]) ? 1 : 0;
+    return k;
+}
 
 // The product forward (fdct8.hip): fdct8_quant_v3 over every plane of ps, every plan.
 hipError_t launch_fdct8_quant(const PlaneSet &ps, const DevTables *dev, int adaptive, unsigned long long *fallbacks,

@@ -24,35 +24,8 @@
 
 namespace dctq {
 
-// The grid of launch_persistent (f64_pair.hip): up to 64 x the resident workgroups.
+// The grid (launch_persistent): up to 64 x the resident workgroups, as the paired kernels of f64_pair.hip.
 constexpr int kDecodeGridMult = 64;
-
-__device__ __forceinline__ const int16_t *coef_in(const DecodeSet &ds, int k) {
-    const int16_t *c = ds.coef[0];
-#pragma unroll
-    for (int i = 1; i < kMaxPlanes; ++i) c = k == i ? ds.coef[i] : c;
-    return c;
-}
-__device__ __forceinline__ const int32_t *var_in(const DecodeSet &ds, int k) {
-    const int32_t *v = ds.var[0];
-#pragma unroll
-    for (int i = 1; i < kMaxPlanes; ++i) v = k == i ? ds.var[i] : v;
-    return v;
-}
-// First global batch of plane k / plane of global batch g (both wave-uniform), as
-// first_of / plane_of of fdct8_core.h over 32-block batches.
-__device__ __forceinline__ uint32_t first_batch(const DecodeSet &ds, int k) {
-    uint32_t f = 0u;
-#pragma unroll
-    for (int i = 1; i < kMaxPlanes; ++i) f = k == i ? ds.first[i] : f;
-    return f;
-}
-__device__ __forceinline__ int plane_of_batch(const DecodeSet &ds, uint32_t g) {
-    int k = 0;
-#pragma unroll
-    for (int i = 1; i < kMaxPlanes; ++i) k += (i < ds.n && g >= ds.first[i]) ? 1 : 0;
-    return k;
-}
 
 // Coefficient rows 4h..4h+3 (16 B each) of block j of global batch g, and its variance
 // numerator; read once, so non-temporal.  Past the plane's end (and past the last
@@ -60,16 +33,16 @@ __device__ __forceinline__ int plane_of_batch(const DecodeSet &ds, uint32_t g) {
 template <bool ADAPTIVE>
 __device__ __forceinline__ void prefetch_coefs(const DecodeSet &ds, uint32_t g, int h, int j, uint4 (&rows)[4],
                                                int32_t &vn) {
-    const int k = plane_of_batch(ds, g);
-    const uint32_t n = (g - first_batch(ds, k)) * 32u + (uint32_t)j;
+    const int k = plane_of(ds, g);
+    const uint32_t n = (g - first_of(ds, k)) * 32u + (uint32_t)j;
     const uint32_t m = n < (uint32_t)ds.pl[k].nblk ? n : 0u;
-    const u4p *src = reinterpret_cast<const u4p *>(coef_in(ds, k) + (size_t)m * 64) + 4 * h;
+    const u4p *src = reinterpret_cast<const u4p *>(coef_of(ds, k) + (size_t)m * 64) + 4 * h;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const u4p t = __builtin_nontemporal_load(src + r);
         rows[r] = make_uint4(t.x, t.y, t.z, t.w);
     }
-    if (ADAPTIVE) vn = __builtin_nontemporal_load(var_in(ds, k) + m);
+    if (ADAPTIVE) vn = __builtin_nontemporal_load(var_of(ds, k) + m);
 }
 
 // Four fp32 pixels -> 4 bytes: clamp to [0, 255] (v_med3_f32), round to nearest even
@@ -95,9 +68,9 @@ __global__ __launch_bounds__(kThreadsP, 4) void decode8(DecodeSet ds, const DevT
     int32_t nvn = 0;
     prefetch_coefs<ADAPTIVE>(ds, g, h, j, nxt, nvn);
     for (; g < nbatch; g += step) {
-        const int k = plane_of_batch(ds, g);
+        const int k = plane_of(ds, g);
         const PlaneArgs &p = ds.pl[k];
-        const uint32_t n = (g - first_batch(ds, k)) * 32u + (uint32_t)j;
+        const uint32_t n = (g - first_of(ds, k)) * 32u + (uint32_t)j;
         const bool valid = n < (uint32_t)p.nblk;
         uint4 cur[4];
 #pragma unroll
@@ -119,7 +92,7 @@ __global__ __launch_bounds__(kThreadsP, 4) void decode8(DecodeSet ds, const DevT
         const uint32_t bx = rem - by * (uint32_t)p.bw;
         uint8_t *base = const_cast<uint8_t *>(p.src);
         if (p.span) {  // kernel argument: wave-uniform.  Every offset inside the plane is < 2^32
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, (int)p.span, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, (int)p.span, kRsrcFlags);
             const uint32_t st = (uint32_t)p.stride;
             const uint32_t off = f * (uint32_t)p.frame_stride + (by * 8u + 4u * (uint32_t)h) * st + bx * 8u;
             if (valid) {
@@ -135,21 +108,18 @@ __global__ __launch_bounds__(kThreadsP, 4) void decode8(DecodeSet ds, const DevT
     }
 }
 
-template <bool A, bool F32>
-static hipError_t launch_dec(const DecodeSet &ds, const DevTables *dev, hipStream_t stream, int num_cus) {
-    static const int per_cu = resident_per_cu(decode8<A, F32>, kThreadsP);
-    const uint32_t nbatch = ds.first[kMaxPlanes];
-    const uint32_t want = (nbatch + kWavesP - 1) / kWavesP;
-    const uint32_t cap = (uint32_t)(num_cus * per_cu * kDecodeGridMult);
-    hipLaunchKernelGGL((decode8<A, F32>), dim3(want < cap ? want : cap), dim3(kThreadsP), 0, stream, ds, dev);
-    return hipGetLastError();
-}
-
 hipError_t launch_decode(const DecodeSet &ds, const DevTables *dev, int adaptive, bool inv_f32, hipStream_t stream,
                          int num_cus) {
-    if (adaptive) return launch_dec<true, false>(ds, dev, stream, num_cus);
-    if (inv_f32) return launch_dec<false, true>(ds, dev, stream, num_cus);
-    return launch_dec<false, false>(ds, dev, stream, num_cus);
+    return with_bools(
+        [&](auto a, auto f32) {
+            if constexpr (a && f32) {
+                return hipErrorInvalidValue;  // never dispatched: the fp32 inverse is the non-adaptive plans'
+            } else {
+                return launch_persistent<decode8<a, f32>, kThreadsP, kWavesP, kDecodeGridMult>(
+                    ds.first[kMaxPlanes], num_cus, stream, ds, dev);
+            }
+        },
+        adaptive != 0, inv_f32 && !adaptive);
 }
 
 }  // namespace dctq

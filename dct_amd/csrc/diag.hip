@@ -26,7 +26,7 @@ __global__ __launch_bounds__(256) void stream12(const u4v *__restrict__ src, cha
         u4v v[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = __builtin_nontemporal_load(src + (size_t)b * 256 + k * 64 + lane);
-        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)b * 8192, 0, 8192, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)b * 8192, 0, 8192, kRsrcFlags);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             __builtin_amdgcn_raw_buffer_store_b128(v[k], rc, lane * 16, k * 1024, AUX);
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void stream124(const u4v *__restrict__ src, ch
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = __builtin_nontemporal_load(src + (size_t)b * 256 + k * 64 + lane);
         const __amdgpu_buffer_rsrc_t rc =
-            __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)b * 24576, 0, 24576, 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)b * 24576, 0, 24576, kRsrcFlags);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -66,9 +66,9 @@ __global__ __launch_bounds__(256) void stream124_split(const u4v *__restrict__ s
         u4v v[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = __builtin_nontemporal_load(src + (size_t)b * 256 + k * 64 + lane);
-        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)b * 8192, 0, 8192, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)b * 8192, 0, 8192, kRsrcFlags);
         const __amdgpu_buffer_rsrc_t rb =
-            __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)nb * 8192 + (size_t)b * 16384, 0, 16384, 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)nb * 8192 + (size_t)b * 16384, 0, 16384, kRsrcFlags);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void stream124_split(const u4v *__restrict__ s
                                                        (k * 2 + m) * 1024, 2);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            if (GROUPS) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), as before the round trip's read-backs
+            if (GROUPS) retire_stores();  // vmcnt(0), as before the round trip's read-backs
 #pragma unroll
             for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void stream124_rows(const uint8_t *__restrict_
                                                       uint32_t nb) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src), (short)0, (int)(nb * 4096u), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src), (short)0, (int)(nb * 4096u), kRsrcFlags);
     constexpr uint32_t kBpr = W ? W / 8 : 64;  // blocks per block row
     const uint32_t nfull = W ? nb * 64u / kBpr * kBpr : nb * 64u;
     const uint32_t nwg = gridDim.x, kwg = (nb + nwg - 1) / nwg, kw = (nb + nwg * 4 - 1) / (nwg * 4);
@@ -120,9 +120,9 @@ __global__ __launch_bounds__(256) void stream124_rows(const uint8_t *__restrict_
         u4v v[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = u4v{r[2 * k].x, r[2 * k].y, r[2 * k + 1].x, r[2 * k + 1].y};
-        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)b * 8192, 0, 8192, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)b * 8192, 0, 8192, kRsrcFlags);
         const __amdgpu_buffer_rsrc_t rb =
-            __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)nb * 8192 + (size_t)b * 16384, 0, 16384, 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)nb * 8192 + (size_t)b * 16384, 0, 16384, kRsrcFlags);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void stream124_rows(const uint8_t *__restrict_
                                                        (k * 2 + m) * 1024, 2);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+            retire_stores();  // vmcnt(0)
 #pragma unroll
             for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void stream124_rows16(const uint8_t *__restric
     constexpr uint32_t kW = 3840, kBpr = kW / 8;
     const int lane = threadIdx.x & 63;
     const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src), (short)0, (int)(nb * 4096u), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src), (short)0, (int)(nb * 4096u), kRsrcFlags);
     const uint32_t nfull = nb * 64u / kBpr * kBpr;
     for (uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6); b < nb; b += gridDim.x * 4) {
         const uint32_t n = (b * 64u + 2u * (uint32_t)(lane & 31)) % nfull;
@@ -158,9 +158,9 @@ __global__ __launch_bounds__(256) void stream124_rows16(const uint8_t *__restric
         u4v v[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + 2 * k * kW, 0, 2);
-        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)b * 8192, 0, 8192, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)b * 8192, 0, 8192, kRsrcFlags);
         const __amdgpu_buffer_rsrc_t rb =
-            __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)nb * 8192 + (size_t)b * 16384, 0, 16384, 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)nb * 8192 + (size_t)b * 16384, 0, 16384, kRsrcFlags);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void stream124_rows16(const uint8_t *__restric
                                                        (k * 2 + m) * 1024, 2);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+            retire_stores();  // vmcnt(0)
 #pragma unroll
             for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256) void stream12_plane(const uint8_t *__restrict_
     constexpr uint32_t kW = 3840, kBpr = kW / 8;
     const int lane = threadIdx.x & 63;
     const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src), (short)0, (int)(nb * 4096u), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src), (short)0, (int)(nb * 4096u), kRsrcFlags);
     const uint32_t nfull = nb * 64u / kBpr * kBpr;
     for (uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6); b < nb; b += gridDim.x * 4) {
         const uint32_t n = (b * 64u + (uint32_t)lane) % nfull;
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256) void stream12_plane(const uint8_t *__restrict_
         u2v2 r[8];
 #pragma unroll
         for (int y = 0; y < 8; ++y) r[y] = __builtin_amdgcn_raw_buffer_load_b64(rs, off + y * kW, 0, 2);
-        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)b * 8192, 0, 8192, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(dst + (size_t)b * 8192, 0, 8192, kRsrcFlags);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const u4v v = u4v{r[2 * k].x, r[2 * k].y, r[2 * k + 1].x, r[2 * k + 1].y};

@@ -22,11 +22,6 @@
 
 namespace dctq {
 
-__device__ __forceinline__ void fence_rows(uint2 (&nxt)[8]) {
-    asm volatile("" : "+v"(nxt[0]), "+v"(nxt[1]), "+v"(nxt[2]), "+v"(nxt[3]), "+v"(nxt[4]), "+v"(nxt[5]),
-                 "+v"(nxt[6]), "+v"(nxt[7])::"memory");
-}
-
 __device__ __forceinline__ uint32_t nz16e(uint32_t w) { return ((w & 0xFFFFu) != 0u) + ((w >> 16) != 0u); }
 
 // Passes of <= 8 tie entries run 8 lanes per entry (exact_grouped<8>): -0.9 %; the wide
@@ -74,11 +69,7 @@ __global__ __launch_bounds__(kThreads, 4) void encode_count_kernel(EncodeSet es,
         u4v q[8];
         stage_chunks(stage, wv, lane, q);
         const int nb = (int)out.nb;
-        {
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(out.base, (short)0, nb * 128, 0x00020000);
-#pragma unroll
-            for (int c = 0; c < 8; ++c) __builtin_amdgcn_raw_buffer_store_b128(q[c], rs, lane * 16, c * 1024, kNtAux);
-        }
+        store_batch<false>(out, q, 0, lane);
         uint32_t run = 0;
 #pragma unroll
         for (int kk = 0; kk < 8; ++kk) {
@@ -95,23 +86,18 @@ __global__ __launch_bounds__(kThreads, 4) void encode_count_kernel(EncodeSet es,
     }
 }
 
-template <typename K, typename... A>
-static hipError_t launch_enc(K kernel, uint32_t nbatch, int num_cus, hipStream_t stream, A... args) {
-    const int per_cu = resident_per_cu(kernel, kThreads);
-    const uint32_t want = (nbatch + kWaves - 1) / kWaves;
-    const uint32_t cap = (uint32_t)(num_cus * per_cu * kEncGridMult);
-    hipLaunchKernelGGL(kernel, dim3(want < cap ? want : cap), dim3(kThreads), 0, stream, args...);
-    return hipGetLastError();
-}
-
 size_t encode_workspace_bytes(long long nbatch) { return rle_scan_workspace_bytes(nbatch); }
 
 hipError_t launch_encode(const EncodeSet &es, const DevTables *dev, int adaptive, uint32_t *offsets, void *symbols,
                          int symbol_bytes, unsigned long long capacity, void *ws, hipStream_t stream, int num_cus) {
     const uint32_t nbatch = es.ps.first[es.ps.n];
     uint32_t *tiles = (uint32_t *)ws;
-    hipError_t e = adaptive ? launch_enc(encode_count_kernel<true>, nbatch, num_cus, stream, es, dev, offsets, tiles)
-                            : launch_enc(encode_count_kernel<false>, nbatch, num_cus, stream, es, dev, offsets, tiles);
+    hipError_t e = with_bools(
+        [&](auto a) {
+            return launch_persistent<encode_count_kernel<a>, kThreads, kWaves, kEncGridMult>(nbatch, num_cus, stream, es,
+                                                                                            dev, offsets, tiles);
+        },
+        adaptive != 0);
     if (e != hipSuccess) return e;
     if ((e = launch_rle_scan(ws, nbatch, stream)) != hipSuccess) return e;
     for (int k = 0; k < es.ps.n; ++k) {

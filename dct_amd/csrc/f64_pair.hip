@@ -216,25 +216,23 @@ __global__ __launch_bounds__(kThreadsP, 4) void idct8_pair(const DevTables *__re
 // the forward 4-5 % slower), profiles/r06/pair_grid_ab/.
 constexpr int kPairGridMult = 64;
 
-template <typename K, typename... A>
-static hipError_t launch_persistent(K kernel, long long nblk, int num_cus, hipStream_t stream, A... args) {
-    const int per_cu = resident_per_cu(kernel, kThreadsP);
-    const long long nbatch = (nblk + 31) / 32;
-    const long long want = (nbatch + kWavesP - 1) / kWavesP;
-    const long long cap = (long long)num_cus * per_cu * kPairGridMult;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(kThreadsP), 0, stream, args...);
-    return hipGetLastError();
-}
+// 32-block batches of nblk blocks, as the kernels count them
+static uint32_t pair_batches(long long nblk) { return (uint32_t)((nblk + 31) >> 5); }
 
 hipError_t launch_fdct8_float_pair(const PlaneArgs &p, const DevTables *dev, float *coef, hipStream_t stream,
                                    int num_cus) {
-    return launch_persistent(fdct8_float_pair, p.nblk, num_cus, stream, p, dev, coef);
+    return launch_persistent<fdct8_float_pair, kThreadsP, kWavesP, kPairGridMult>(pair_batches(p.nblk), num_cus, stream,
+                                                                                  p, dev, coef);
 }
 
 hipError_t launch_idct8_pair(const DevTables *dev, int adaptive, const int16_t *coef, const int32_t *var_num,
                              long long nblk, float *recon, hipStream_t stream, int num_cus) {
-    if (adaptive) return launch_persistent(idct8_pair<true>, nblk, num_cus, stream, dev, coef, var_num, nblk, recon);
-    return launch_persistent(idct8_pair<false>, nblk, num_cus, stream, dev, coef, var_num, nblk, recon);
+    return with_bools(
+        [&](auto a) {
+            return launch_persistent<idct8_pair<a>, kThreadsP, kWavesP, kPairGridMult>(
+                pair_batches(nblk), num_cus, stream, dev, coef, var_num, nblk, recon);
+        },
+        adaptive != 0);
 }
 
 }  // namespace dctq

@@ -62,8 +62,7 @@ __global__ __launch_bounds__(kFThreads, 4) void fdct8_quant_v3(PlaneSet ps, cons
     uint32_t g = blockIdx.x * kFWaves + wv;
     uint2 nxt[8];
     prefetch_batch(ps, g, lane, nxt);
-    asm volatile("" : "+v"(nxt[0]), "+v"(nxt[1]), "+v"(nxt[2]), "+v"(nxt[3]), "+v"(nxt[4]), "+v"(nxt[5]),
-                 "+v"(nxt[6]), "+v"(nxt[7])::"memory");
+    fence_rows(nxt);
     uint32_t resolved = 0;
     for (; g < nbatch; g += step) {
         const uint32_t gnext = g + step;
@@ -80,50 +79,34 @@ __global__ __launch_bounds__(kFThreads, 4) void fdct8_quant_v3(PlaneSet ps, cons
         forward_flags_batch<ADAPTIVE, VAR>(dev, cur, stage, lane, wv, b * 64 + lane < (uint32_t)p.nblk, var_num, mlo,
                                            mhi);
         // the prefetch wait (retires the previous batch's stores too), then LDS reads
-        asm volatile("" : "+v"(nxt[0]), "+v"(nxt[1]), "+v"(nxt[2]), "+v"(nxt[3]), "+v"(nxt[4]), "+v"(nxt[5]),
-                     "+v"(nxt[6]), "+v"(nxt[7])::"memory");
+        fence_rows(nxt);
         resolved += resolve_ties_compact<ADAPTIVE, kV3Group8, (VAR || STATS) ? 0 : kV3Wide>(
             &tab, cur, stage, scr + wv * 64, lane, wv, mlo, mhi);
         wave_sync();
         u4v val[8];
         stage_chunks(stage, wv, lane, val);
+        // store_batch<VAR>, spelled out (fdct8_core.h)
         const __amdgpu_buffer_rsrc_t rs =
-            __builtin_amdgcn_make_buffer_rsrc(out.base, (short)0, (int)(out.nb * 128u), 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc(out.base, (short)0, (int)(out.nb * 128u), kRsrcFlags);
 #pragma unroll
-        for (int c = 0; c < 8; ++c) __builtin_amdgcn_raw_buffer_store_b128(val[c], rs, lane * 16, c * 1024, kStoreAux);
+        for (int c = 0; c < 8; ++c) __builtin_amdgcn_raw_buffer_store_b128(val[c], rs, lane * 16, c * 1024, kNtAux);
         if (VAR) {
             const __amdgpu_buffer_rsrc_t rv =
-                __builtin_amdgcn_make_buffer_rsrc(out.var, (short)0, (int)(out.nb * 4u), 0x00020000);
-            __builtin_amdgcn_raw_buffer_store_b32(var_num, rv, lane * 4, 0, kStoreAux);
+                __builtin_amdgcn_make_buffer_rsrc(out.var, (short)0, (int)(out.nb * 4u), kRsrcFlags);
+            __builtin_amdgcn_raw_buffer_store_b32(var_num, rv, lane * 4, 0, kNtAux);
         }
     }
     if (STATS && resolved) atomicAdd(fallbacks, (unsigned long long)resolved);
 }
 
-template <bool A, bool V, bool S>
-static hipError_t launch_v3(const PlaneSet &ps, const DevTables *dev, unsigned long long *fb, hipStream_t stream,
-                            int num_cus) {
-    static const int per_cu = resident_per_cu(fdct8_quant_v3<A, V, S>, kFThreads);
-    const uint32_t nbatch = ps.first[ps.n];
-    const uint32_t want = (nbatch + kFWaves - 1) / kFWaves;
-    const uint32_t cap = (uint32_t)(num_cus * per_cu * kV3GridMult);
-    hipLaunchKernelGGL((fdct8_quant_v3<A, V, S>), dim3(want < cap ? want : cap), dim3(kFThreads), 0, stream, ps, dev, fb);
-    return hipGetLastError();
-}
-
 hipError_t launch_fdct8_quant(const PlaneSet &ps, const DevTables *dev, int adaptive, unsigned long long *fallbacks,
                               hipStream_t stream, int num_cus) {
-    const bool a = adaptive != 0, v = ps.var[0] != nullptr, s = fallbacks != nullptr;
-    if (a) {
-        if (v) return s ? launch_v3<true, true, true>(ps, dev, fallbacks, stream, num_cus)
-                        : launch_v3<true, true, false>(ps, dev, fallbacks, stream, num_cus);
-        return s ? launch_v3<true, false, true>(ps, dev, fallbacks, stream, num_cus)
-                 : launch_v3<true, false, false>(ps, dev, fallbacks, stream, num_cus);
-    }
-    if (v) return s ? launch_v3<false, true, true>(ps, dev, fallbacks, stream, num_cus)
-                    : launch_v3<false, true, false>(ps, dev, fallbacks, stream, num_cus);
-    return s ? launch_v3<false, false, true>(ps, dev, fallbacks, stream, num_cus)
-             : launch_v3<false, false, false>(ps, dev, fallbacks, stream, num_cus);
+    return with_bools(
+        [&](auto a, auto v, auto s) {
+            return launch_persistent<fdct8_quant_v3<a, v, s>, kFThreads, kFWaves, kV3GridMult>(
+                ps.first[ps.n], num_cus, stream, ps, dev, fallbacks);
+        },
+        adaptive != 0, ps.var[0] != nullptr, fallbacks != nullptr);
 }
 
 }  // namespace dctq

@@ -92,10 +92,6 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u2v __attribute__((ext_vector_type(2)));
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));
 constexpr int kPitch2 = 136;   // bytes per block in the stage: 2-way (free) conflicts for the b32 writes
-// Cache policy of the bulk coefficient stores: non-temporal (kNtAux), -15 % kernel
-// time on the 4K stream (profiles/r01/store_policy.md); the written lines are never
-// re-read by this kernel except by tie patches, which come after a vmcnt(0).
-constexpr int kStoreAux = kNtAux;
 
 template <int K>
 __device__ __forceinline__ float cvt_ubyte(uint32_t w) {
@@ -120,7 +116,7 @@ __device__ __forceinline__ void load_rows(const PlaneArgs &p, uint32_t n, uint2 
     if constexpr (BUF) {
         if (p.span) {  // kernel argument: wave-uniform
             const __amdgpu_buffer_rsrc_t rs =
-                __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.src), (short)0, (int)p.span, 0x00020000);
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.src), (short)0, (int)p.span, kRsrcFlags);
             const uint32_t off = (uint32_t)(px - p.src), st = (uint32_t)p.stride;
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
@@ -135,32 +131,6 @@ __device__ __forceinline__ void load_rows(const PlaneArgs &p, uint32_t n, uint2 
         const u2v t = __builtin_nontemporal_load(reinterpret_cast<const u2v *>(px + r * p.stride));
         rows[r] = make_uint2(t.x, t.y);
     }
-}
-
-// Coefficient output of plane k (k wave-uniform or not: a select chain, no indexed kernarg loads).
-__device__ __forceinline__ int16_t *coef_of(const PlaneSet &ps, uint32_t k) {
-    int16_t *c = ps.coef[0];
-#pragma unroll
-    for (int i = 1; i < kMaxPlanes; ++i) c = k == (uint32_t)i ? ps.coef[i] : c;
-    return c;
-}
-
-// First global batch of plane k (wave-uniform k): a select chain over the batch
-// prefixes, which sit in SGPRs for the whole kernel -- an indexed kernel-argument
-// load here was one more scalar-cache round trip in front of every prefetch.
-__device__ __forceinline__ uint32_t first_of(const PlaneSet &ps, int k) {
-    uint32_t f = 0u;
-#pragma unroll
-    for (int i = 1; i < kMaxPlanes; ++i) f = k == i ? ps.first[i] : f;
-    return f;
-}
-
-// Plane of global batch g (wave-uniform).
-__device__ __forceinline__ int plane_of(const PlaneSet &ps, uint32_t g) {
-    int k = 0;
-#pragma unroll
-    for (int i = 1; i < kMaxPlanes; ++i) k += (i < ps.n && g >= ps.first[i]) ? 1 : 0;
-    return k;
 }
 
 // The arithmetic of one 64-block batch (one block per lane): u8 rows -> fp32,
@@ -207,7 +177,7 @@ __device__ __forceinline__ void fdct8_compute(const DevTables *__restrict__ dev,
     f2 sc2 = {1.0f, 1.0f};
     if (ADAPTIVE) {
         // The fast path only needs 1/(2-nv) within its guard band (4.5u relative for
-        // adaptive plans, api.hip fill_fast_tables): nv through a multiply by
+        // adaptive plans, plan_tables.hip fill_fast_tables): nv through a multiply by
         // fl(0.001) instead of the reference's division (relative error ~2^-52),
         // then fl32(2-nv) (0.5u) and v_rcp_f32 (1 ulp = 2u) -- two fp64 divisions
         // per lane per batch were ~8 % of the adaptive kernel's time.  The exact
@@ -646,8 +616,30 @@ __device__ __forceinline__ BatchOut batch_out(const PlaneSet &ps, int k, uint32_
     return o;
 }
 
-// vmcnt(0): the wave's stores have read their data VGPRs (and left the CU).
-__device__ __forceinline__ void retire_stores() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+// The batch's 8 x 1 KiB coefficient chunks (stage_chunks) and, with VAR, its var_num:
+// through descriptors that end at the batch's last valid block, so the stores are
+// unconditional.  Non-temporal (kNtAux): -15 % kernel time on the 4K stream
+// (profiles/r01/store_policy.md).  fdct8_quant_v3 and roundtrip8 spell the same stores
+// out: through this helper their machine code differs (two instructions reordered).
+template <bool VAR>
+__device__ __forceinline__ void store_batch(const BatchOut &out, const u4v (&val)[8], int32_t var_num, int lane) {
+    const __amdgpu_buffer_rsrc_t rs =
+        __builtin_amdgcn_make_buffer_rsrc(out.base, (short)0, (int)(out.nb * 128u), kRsrcFlags);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) __builtin_amdgcn_raw_buffer_store_b128(val[c], rs, lane * 16, c * 1024, kNtAux);
+    if (VAR) {
+        const __amdgpu_buffer_rsrc_t rv =
+            __builtin_amdgcn_make_buffer_rsrc(out.var, (short)0, (int)(out.nb * 4u), kRsrcFlags);
+        __builtin_amdgcn_raw_buffer_store_b32(var_num, rv, lane * 4, 0, kNtAux);
+    }
+}
+
+// Consume the prefetched rows: the wait for their loads -- which on gfx950 (one
+// in-order counter for loads and stores) retires every older store too -- lands here.
+__device__ __forceinline__ void fence_rows(uint2 (&nxt)[8]) {
+    asm volatile("" : "+v"(nxt[0]), "+v"(nxt[1]), "+v"(nxt[2]), "+v"(nxt[3]), "+v"(nxt[4]), "+v"(nxt[5]),
+                 "+v"(nxt[6]), "+v"(nxt[7])::"memory");
+}
 
 // Rows of global batch gn.  Past the end (a wave's last batch), SKIP loads
 // nothing: the rows would be unused, and with the grid 8x the resident one every

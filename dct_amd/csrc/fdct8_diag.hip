@@ -266,7 +266,7 @@ __device__ __forceinline__ void drain_queue(const PlaneSet &ps, const DevTables 
                                             const uint16_t *qc, const uint4 *ring, int &qn, int lane,
                                             unsigned long long *fallbacks) {
     // the wave's own coefficient stores (and its stash stores) must land first
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    retire_stores();  // vmcnt(0)
     const int take = qn < 64 ? qn : 64;
     // the planes' output pointers in SGPRs: selected per lane with v_cndmask (left
     // to itself the compiler indexes the kernel-argument array with a per-lane
@@ -343,8 +343,7 @@ __device__ __forceinline__ void fdct8_batch(const PlaneSet &ps, const DevTables 
     // the top of the next batch, where LLVM orders the youngest load against
     // younger loads only and emits vmcnt(0) -- which on gfx950 (one in-order
     // counter for loads and stores) also drains this batch's stores.
-    asm volatile("" : "+v"(nxt[0]), "+v"(nxt[1]), "+v"(nxt[2]), "+v"(nxt[3]), "+v"(nxt[4]), "+v"(nxt[5]),
-                 "+v"(nxt[6]), "+v"(nxt[7])::"memory");
+    fence_rows(nxt);
 
     // A full round of entries from earlier batches drains HERE, before this
     // batch's stores are issued: vmcnt counts in issue order, so a drain after
@@ -378,7 +377,7 @@ __device__ __forceinline__ void fdct8_batch(const PlaneSet &ps, const DevTables 
         // stores are unconditional (predicated stores made the waitcnt pass give
         // up and wait vmcnt(0) at the loop latch).
         const __amdgpu_buffer_rsrc_t rs =
-            __builtin_amdgcn_make_buffer_rsrc(out.base, (short)0, (int)(out.nb * 128u), 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc(out.base, (short)0, (int)(out.nb * 128u), kRsrcFlags);
         const uint2 *st64 = reinterpret_cast<const uint2 *>(stage) + wv * 64 * (kPitch2 / 8);
         // all 8 chunks into distinct registers first, one voffset register and
         // per-store soffsets: a store's VGPR operands must not be overwritten
@@ -396,12 +395,12 @@ __device__ __forceinline__ void fdct8_batch(const PlaneSet &ps, const DevTables 
             for (int k = 0; k < 8; ++k) asm volatile("" ::"v"(val[k]));
         } else {
 #pragma unroll
-            for (int k = 0; k < 8; ++k) __builtin_amdgcn_raw_buffer_store_b128(val[k], rs, lane * 16, k * 1024, kStoreAux);
+            for (int k = 0; k < 8; ++k) __builtin_amdgcn_raw_buffer_store_b128(val[k], rs, lane * 16, k * 1024, kNtAux);
         }
         if (VAR) {
             const __amdgpu_buffer_rsrc_t rv =
-                __builtin_amdgcn_make_buffer_rsrc(out.var, (short)0, (int)(out.nb * 4u), 0x00020000);
-            __builtin_amdgcn_raw_buffer_store_b32(var_num, rv, lane * 4, 0, kStoreAux);
+                __builtin_amdgcn_make_buffer_rsrc(out.var, (short)0, (int)(out.nb * 4u), kRsrcFlags);
+            __builtin_amdgcn_raw_buffer_store_b32(var_num, rv, lane * 4, 0, kNtAux);
         }
     }
 
@@ -471,8 +470,7 @@ __global__ __launch_bounds__(kFThreads, 4) void fdct8_quant_v2(PlaneSet ps, Fast
     }
     // same fence as at the end of a batch: the loop header then sees no load in
     // flight on either incoming edge and needs no wait at all
-    asm volatile("" : "+v"(nxt[0]), "+v"(nxt[1]), "+v"(nxt[2]), "+v"(nxt[3]), "+v"(nxt[4]), "+v"(nxt[5]),
-                 "+v"(nxt[6]), "+v"(nxt[7])::"memory");
+    fence_rows(nxt);
     for (; g < nbatch; g += step)
         fdct8_batch<ADAPTIVE, VAR, STATS>(ps, dev, &tab, fallbacks, stage, qb, qc, ring, qn, nxt, g, step, lane, wv);
     if (DCTQ_ABLATE & 16) qn = 0;
@@ -480,17 +478,6 @@ __global__ __launch_bounds__(kFThreads, 4) void fdct8_quant_v2(PlaneSet ps, Fast
     while (qn > 0) drain_queue<ADAPTIVE, STATS>(ps, dev, qb, qc, ring, qn, lane, fallbacks);
 }
 
-
-#define DCTQ_SELECT(KERN, A, V, S, ...)                                          \
-    do {                                                                         \
-        if (A) {                                                                 \
-            if (V) { if (S) KERN<true, true, true> __VA_ARGS__; else KERN<true, true, false> __VA_ARGS__; } \
-            else { if (S) KERN<true, false, true> __VA_ARGS__; else KERN<true, false, false> __VA_ARGS__; } \
-        } else {                                                                 \
-            if (V) { if (S) KERN<false, true, true> __VA_ARGS__; else KERN<false, true, false> __VA_ARGS__; } \
-            else { if (S) KERN<false, false, true> __VA_ARGS__; else KERN<false, false, false> __VA_ARGS__; } \
-        }                                                                        \
-    } while (0)
 
 template <bool A, bool V, bool S>
 static hipError_t launch_v1(const PlaneSet &ps, const FastTables &t, const DevTables *dev, unsigned long long *fb,
@@ -504,14 +491,10 @@ static hipError_t launch_v1(const PlaneSet &ps, const FastTables &t, const DevTa
 template <bool A, bool V, bool S>
 static hipError_t launch_v2(const PlaneSet &ps, const FastTables &t, const DevTables *dev, unsigned long long *fb,
                             hipStream_t stream, int num_cus, const RingSource &rs) {
-    static const int per_cu = resident_per_cu(fdct8_quant_v2<A, V, S>, kFThreads);
-    const uint32_t nbatch = ps.first[ps.n];
-    const uint32_t want = (nbatch + kFWaves - 1) / kFWaves;
-    const uint32_t cap = (uint32_t)(num_cus * per_cu * kV2GridMult);
-    const uint32_t grid = want < cap ? want : cap;
+    const uint32_t grid = persistent_grid<fdct8_quant_v2<A, V, S>, kFThreads, kFWaves>(ps.first[ps.n], num_cus, kV2GridMult);
     // the stash is sized to THIS grid (every workgroup owns its waves' slots) and
     // handed out by the caller per (device, stream): launches on one stream are
-    // ordered, so they share it (api.hip stash_for)
+    // ordered, so they share it (stash_for, below)
     void *ring = rs.get(rs.ctx, fdct8_ring_bytes((int)grid));
     if (!ring) return hipErrorOutOfMemory;
     hipLaunchKernelGGL((fdct8_quant_v2<A, V, S>), dim3(grid), dim3(kFThreads), 0, stream, ps, t, dev, fb, (uint4 *)ring);
@@ -563,8 +546,7 @@ __global__ __launch_bounds__(kFThreads, 4) void fdct8_movement(PlaneSet ps, cons
     uint32_t g = blockIdx.x * kFWaves + wv;
     uint2 nxt[8];
     prefetch_batch(ps, g, lane, nxt);
-    asm volatile("" : "+v"(nxt[0]), "+v"(nxt[1]), "+v"(nxt[2]), "+v"(nxt[3]), "+v"(nxt[4]), "+v"(nxt[5]),
-                 "+v"(nxt[6]), "+v"(nxt[7])::"memory");
+    fence_rows(nxt);
     for (; g < nbatch; g += step) {
         const int k = plane_of(ps, g);
         const uint32_t b = g - first_of(ps, k);
@@ -589,15 +571,11 @@ __global__ __launch_bounds__(kFThreads, 4) void fdct8_movement(PlaneSet ps, cons
                 for (int i = 0; i < 8; ++i) st32[i * 4 + cp] = cp & 1 ? cur[i].y : cur[i].x ^ (uint32_t)cp;
         }
         if (DCTQ_MV3_SLEEP) __builtin_amdgcn_s_sleep(DCTQ_MV3_SLEEP);  // A/B: the arithmetic's latency slack
-        asm volatile("" : "+v"(nxt[0]), "+v"(nxt[1]), "+v"(nxt[2]), "+v"(nxt[3]), "+v"(nxt[4]), "+v"(nxt[5]),
-                     "+v"(nxt[6]), "+v"(nxt[7])::"memory");
+        fence_rows(nxt);
         wave_sync();
         u4v val[8];
         stage_chunks(stage, wv, lane, val);
-        const __amdgpu_buffer_rsrc_t rs =
-            __builtin_amdgcn_make_buffer_rsrc(out.base, (short)0, (int)(out.nb * 128u), 0x00020000);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) __builtin_amdgcn_raw_buffer_store_b128(val[c], rs, lane * 16, c * 1024, kStoreAux);
+        store_batch<false>(out, val, 0, lane);
     }
 }
 
@@ -615,8 +593,7 @@ __global__ __launch_bounds__(kFThreads, 4) void fdct8_movement_v2(PlaneSet ps) {
         const int k0 = plane_of(ps, g);
         load_rows(ps.pl[k0], (g - first_of(ps, k0)) * 64 + lane, nxt);
     }
-    asm volatile("" : "+v"(nxt[0]), "+v"(nxt[1]), "+v"(nxt[2]), "+v"(nxt[3]), "+v"(nxt[4]), "+v"(nxt[5]),
-                 "+v"(nxt[6]), "+v"(nxt[7])::"memory");
+    fence_rows(nxt);
     for (; g < nbatch; g += step) {
         const int k = plane_of(ps, g);
         const PlaneArgs &p = ps.pl[k];
@@ -631,33 +608,28 @@ __global__ __launch_bounds__(kFThreads, 4) void fdct8_movement_v2(PlaneSet ps) {
             mine[2 * r] = cur[r];
             mine[2 * r + 1] = make_uint2(cur[r].y, cur[r].x);
         }
-        asm volatile("" : "+v"(nxt[0]), "+v"(nxt[1]), "+v"(nxt[2]), "+v"(nxt[3]), "+v"(nxt[4]), "+v"(nxt[5]),
-                     "+v"(nxt[6]), "+v"(nxt[7])::"memory");
+        fence_rows(nxt);
         wave_sync();
         const uint32_t left = (uint32_t)p.nblk - b * 64;
         const uint32_t nb = left < 64u ? left : 64u;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            reinterpret_cast<char *>(coef_of(ps, k)) + (size_t)b * 64 * 128, (short)0, (int)(nb * 128u), 0x00020000);
+            reinterpret_cast<char *>(coef_of(ps, k)) + (size_t)b * 64 * 128, (short)0, (int)(nb * 128u), kRsrcFlags);
         u4v val[8];
         stage_chunks(stage, wv, lane, val);
 #pragma unroll
-        for (int q = 0; q < 8; ++q) __builtin_amdgcn_raw_buffer_store_b128(val[q], rs, lane * 16, q * 1024, kStoreAux);
+        for (int q = 0; q < 8; ++q) __builtin_amdgcn_raw_buffer_store_b128(val[q], rs, lane * 16, q * 1024, kNtAux);
     }
 }
 
 hipError_t launch_fdct8_movement(const PlaneSet &ps, const DevTables *dev, hipStream_t stream, int num_cus, int shape,
                                  int grid_mult) {
     const uint32_t nbatch = ps.first[ps.n];
-    const uint32_t want = (nbatch + kFWaves - 1) / kFWaves;
-    if (shape == 2) {
-        static const int per_cu = resident_per_cu(fdct8_movement_v2, kFThreads);
-        const uint32_t cap = (uint32_t)(num_cus * per_cu * kV2GridMult);  // the same grid as launch_v2
-        hipLaunchKernelGGL(fdct8_movement_v2, dim3(want < cap ? want : cap), dim3(kFThreads), 0, stream, ps);
-    } else {
-        static const int per_cu = resident_per_cu(fdct8_movement, kFThreads);
-        const uint32_t cap = (uint32_t)(num_cus * per_cu * (grid_mult > 0 ? grid_mult : kV3GridMult));  // launch_v3's
-        hipLaunchKernelGGL(fdct8_movement, dim3(want < cap ? want : cap), dim3(kFThreads), 0, stream, ps, dev);
-    }
+    if (shape == 2)  // the same grid as launch_v2
+        return launch_persistent<fdct8_movement_v2, kFThreads, kFWaves, kV2GridMult>(nbatch, num_cus, stream, ps);
+    // fdct8_quant_v3's grid, or the caller's multiplier
+    const uint32_t grid = persistent_grid<fdct8_movement, kFThreads, kFWaves>(nbatch, num_cus,
+                                                                              grid_mult > 0 ? grid_mult : kV3GridMult);
+    hipLaunchKernelGGL(fdct8_movement, dim3(grid), dim3(kFThreads), 0, stream, ps, dev);
     return hipGetLastError();
 }
 
@@ -794,8 +766,7 @@ __global__ __launch_bounds__(kThreads, kRtOcc) void roundtrip_movement(RoundTrip
     uint32_t g = blockIdx.x * kWaves + wv;
     uint2 nxt[8];
     prefetch_batch(ps, g, lane, nxt);
-    asm volatile("" : "+v"(nxt[0]), "+v"(nxt[1]), "+v"(nxt[2]), "+v"(nxt[3]), "+v"(nxt[4]), "+v"(nxt[5]),
-                 "+v"(nxt[6]), "+v"(nxt[7])::"memory");
+    fence_rows(nxt);
     char *wstage = reinterpret_cast<char *>(stage) + wv * 64 * kPitch2;
     for (; g < nbatch; g += step) {
         const int k = plane_of(ps, g);
@@ -818,12 +789,7 @@ __global__ __launch_bounds__(kThreads, kRtOcc) void roundtrip_movement(RoundTrip
         const uint32_t nb = out.nb;
         u4v val[8];
         stage_chunks(stage, wv, lane, val);
-        {
-            const __amdgpu_buffer_rsrc_t rs =
-                __builtin_amdgcn_make_buffer_rsrc(out.base, (short)0, (int)(nb * 128u), 0x00020000);
-#pragma unroll
-            for (int c = 0; c < 8; ++c) __builtin_amdgcn_raw_buffer_store_b128(val[c], rs, lane * 16, c * 1024, kNtAux);
-        }
+        store_batch<false>(out, val, 0, lane);
         char *mine = wstage + j * kPitchP + h * 128;
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
@@ -840,12 +806,9 @@ __global__ __launch_bounds__(kThreads, kRtOcc) void roundtrip_movement(RoundTrip
 }
 
 hipError_t launch_roundtrip_movement(const RoundTripSet &rt, hipStream_t stream, int num_cus) {
-    static const int per_cu = resident_per_cu(roundtrip_movement, kThreads);
-    const uint32_t nbatch = rt.ps.first[rt.ps.n];
-    const uint32_t want = (nbatch + kWaves - 1) / kWaves;
-    const uint32_t cap = (uint32_t)(num_cus * per_cu * kRtGridMult);  // the same grid as launch_rt
-    hipLaunchKernelGGL(roundtrip_movement, dim3(want < cap ? want : cap), dim3(kThreads), 0, stream, rt);
-    return hipGetLastError();
+    // the same grid as roundtrip8
+    return launch_persistent<roundtrip_movement, kThreads, kWaves, kRtGridMult>(rt.ps.first[rt.ps.n], num_cus, stream,
+                                                                                rt);
 }
 
 
@@ -975,14 +938,15 @@ int diag_forward_quant(const dctq_plan *plan, const dctq::PlaneSet &ps, hipStrea
     StashCtx sc{plan->device, stream, hipSuccess};
     hipError_t e;
     {
-        const bool a = plan->adaptive != 0, v = ps.var[0] != nullptr, s = plan->fallbacks != nullptr;
         std::lock_guard<std::mutex> stash_guard(g_stash_mu);
-        if (plan->variant == 1) {
-            DCTQ_SELECT(e = dctq::launch_v1, a, v, s, (ps, plan->fast, plan->dev, plan->fallbacks, stream));
-        } else {
-            DCTQ_SELECT(e = dctq::launch_v2, a, v, s, (ps, plan->fast, plan->dev, plan->fallbacks, stream,
-                                                       plan->num_cus, dctq::RingSource{stash_for, &sc}));
-        }
+        e = dctq::with_bools(
+            [&](auto a, auto v, auto s) {
+                if (plan->variant == 1)
+                    return dctq::launch_v1<a, v, s>(ps, plan->fast, plan->dev, plan->fallbacks, stream);
+                return dctq::launch_v2<a, v, s>(ps, plan->fast, plan->dev, plan->fallbacks, stream, plan->num_cus,
+                                                dctq::RingSource{stash_for, &sc});
+            },
+            plan->adaptive != 0, ps.var[0] != nullptr, plan->fallbacks != nullptr);
     }
     if (sc.err != hipSuccess) return dctq::fail(DCTQ_ENOMEM, "tie-path stash", sc.err);
     HIPCHK(e, "fdct8_quant variant launch");
@@ -1009,7 +973,7 @@ int dctq_diag_forward_quant_planes(const dctq_plan *plan, const dctq_plane *plan
 
 int dctq_diag_forward_float(const dctq_plan *plan, const dctq_plane *src, float *coef, void *stream) {
     if (!plan || plan->variant != 1) return dctq_forward_float(plan, src, coef, stream);
-    DCTQ_LAUNCH(stream, 3);
+    DCTQ_LAUNCH(stream, dctq::kEntryForwardFloat);
     if (int rc = dctq::check_plan(plan)) return rc;
     if (!coef || ((uintptr_t)coef) % 16) return dctq::fail(DCTQ_EINVAL, "coef NULL or not 16-byte aligned");
     dctq::PlaneArgs a;
@@ -1021,7 +985,7 @@ int dctq_diag_forward_float(const dctq_plan *plan, const dctq_plane *src, float 
 int dctq_diag_inverse(const dctq_plan *plan, const int16_t *coef, const int32_t *var_num, long long nblocks,
                       float *recon, void *stream) {
     if (!plan || plan->variant != 1) return dctq_inverse(plan, coef, var_num, nblocks, recon, stream);
-    DCTQ_LAUNCH(stream, 4);
+    DCTQ_LAUNCH(stream, dctq::kEntryInverse);
     if (int rc = dctq::check_plan(plan)) return rc;
     if (!coef || !recon) return dctq::fail(DCTQ_EINVAL, "coef/recon is NULL");
     if (plan->adaptive && !var_num) return dctq::fail(DCTQ_EINVAL, "adaptive inverse needs var_num");

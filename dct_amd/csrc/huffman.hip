@@ -216,7 +216,7 @@ __device__ __forceinline__ void tile_dma(const int16_t *coef, long long t, long 
     const long long left = nblk - t * 64;
     const int nb = left < 64 ? (int)left : 64;
     const uint64_t a = (uint64_t)(coef + t * 64 * 64);
-    const i4 rs = {(int)(uint32_t)a, (int)((a >> 32) & 0xFFFFu), nb * 128, 0x00020000};  // as make_buffer_rsrc
+    const i4 rs = {(int)(uint32_t)a, (int)((a >> 32) & 0xFFFFu), nb * 128, kRsrcFlags};  // as make_buffer_rsrc
     // piece (l & 7) ^ (b >> 1 & 7) of block b = 8c + (l >> 3) sits at byte 1024 c + (base ^ 64 (c & 1))
     int base = ((lane >> 3) << 7) | (((lane & 7) ^ (lane >> 4)) << 4);
     asm volatile("" : "+v"(base));  // computed here: eight loop-invariant offsets hoisted out of the loop spilled
@@ -247,7 +247,7 @@ __device__ __forceinline__ void tile_dma(const int16_t *coef, long long t, long 
 template <int N, bool FWD = false, typename NextTile>
 __device__ __forceinline__ void sparse_runs(char *mine, const Hist &h, int lane, uint32_t &nodes, uint32_t &lmax,
                                             NextTile next_tile, const uint32_t (&d)[32]) {
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): every lane has its row before the columns overwrite the tile
+    lgkm_wait();  // lgkmcnt(0): every lane has its row before the columns overwrite the tile
     __builtin_amdgcn_wave_barrier();
     // branch-free compaction: every value is written at the next slot, which advances
     // only past a nonzero (a zero's write is overwritten or lies past `pos`).  The
@@ -289,7 +289,7 @@ __device__ __forceinline__ void sparse_runs(char *mine, const Hist &h, int lane,
             b[k] = (uint32_t)k < pos ? v : kSent;
         }
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the keys are in registers, the stage is free
+    lgkm_wait();  // lgkmcnt(0): the keys are in registers, the stage is free
     __builtin_amdgcn_wave_barrier();
     next_tile();
     sort_net<N>(b);
@@ -305,7 +305,7 @@ __device__ __forceinline__ void dense_runs(char *mine, const Hist &h, int lane, 
         a[2 * h] = (d[h] << 16) - 1u;
         a[2 * h + 1] = (d[h] & 0xFFFF0000u) - 1u;
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the row is in registers, the stage is free
+    lgkm_wait();  // lgkmcnt(0): the row is in registers, the stage is free
     __builtin_amdgcn_wave_barrier();
     next_tile();
     sort_net<64>(a);
@@ -344,7 +344,7 @@ __device__ __forceinline__ void narrow_leaves(char *ctr, int lane, int wv, int32
                                               bool last_zero, NextTile next_tile, NarrowLeaves &L,
                                               const uint32_t (&d)[32]) {
     // the row is in registers and the stage is free: the next tile streams in meanwhile
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+    lgkm_wait();  // lgkmcnt(0)
     next_tile();
     typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
     const uint32_t base = (uint32_t)(lane * 4);  // byte 0 of the lane's dword in every row
@@ -766,7 +766,7 @@ __global__ __launch_bounds__(kHufThreads, kHufMinWaves) void huffman_bits_kernel
     const long long stride = (long long)gridDim.x * kHufWaves;
     long long t = (long long)blockIdx.x * kHufWaves + wv;
     auto store_bits = [&](uint32_t out, long long tt, int n) {
-        const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(bits + tt * 64, (short)0, n * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(bits + tt * 64, (short)0, n * 4, kRsrcFlags);
         __builtin_amdgcn_raw_buffer_store_b32(out, rb, lane * 4, 0, kHufBitsAux);
     };
     if (t < ntiles) tile_dma(coef, t, nblk, mine, lane);
@@ -775,14 +775,14 @@ __global__ __launch_bounds__(kHufThreads, kHufMinWaves) void huffman_bits_kernel
         const int nb = left < 64 ? (int)left : 64;
         // this tile's DMA has landed, and the previous tile's bits store has left
         // (one in-order vmcnt) before LDS reads land in VGPRs (the store-data hazard)
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+        retire_stores();  // vmcnt(0)
         __builtin_amdgcn_wave_barrier();
         if (nb < 64) {  // the launch's last tile: blocks past the end are empty (every path reads them)
             if (lane >= nb) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) *reinterpret_cast<uint4 *>(mine + lane * 128 + k * 16) = make_uint4(0, 0, 0, 0);
             }
-            __builtin_amdgcn_s_waitcnt(0xC07F);
+            lgkm_wait();
             __builtin_amdgcn_wave_barrier();
         }
         auto next_tile = [&] {
@@ -845,7 +845,7 @@ __global__ __launch_bounds__(kHufThreads, kHufMinWaves) void huffman_from_pixels
         const int nb = (uint32_t)p.nblk - b * 64 < 64u ? (int)((uint32_t)p.nblk - b * 64) : 64;
         // the rows are in, and the previous batch's bits store has left before
         // LDS reads land in VGPRs (the store-data hazard)
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+        retire_stores();  // vmcnt(0)
         uint32_t mlo, mhi;
         int32_t var_num;
         fdct8_compute<ADAPTIVE, false>(dev, cur, stage, lane, wv, mlo, mhi, var_num);
@@ -860,16 +860,16 @@ __global__ __launch_bounds__(kHufThreads, kHufMinWaves) void huffman_from_pixels
 #pragma unroll
                 for (int q = 0; q < 16; ++q) *reinterpret_cast<uint2 *>(mine + lane * kPitch2 + 8 * q) = make_uint2(0, 0);
             }
-            __builtin_amdgcn_s_waitcnt(0xC07F);
+            lgkm_wait();
             wave_sync();
         }
         const uint32_t out = tile_bits<true>(mine, ctr, lane, wv, nb, [] {});
         // (pinning this destination in SGPRs at the top, as the forward kernels do, spilled 8 B here)
         const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
-            bits + es.blk_first[k] + (size_t)b * 64, (short)0, nb * 4, 0x00020000);
+            bits + es.blk_first[k] + (size_t)b * 64, (short)0, nb * 4, kRsrcFlags);
         __builtin_amdgcn_raw_buffer_store_b32(out, rb, lane * 4, 0, kHufBitsAux);
         // tile_bits leaves the stage to the next batch's forward only after its own reads
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        lgkm_wait();
         wave_sync();
     }
 }
@@ -881,12 +881,12 @@ hipError_t launch_huffman_from_pixels(const EncodeSet &es, const DevTables *dev,
     const long long cap = (long long)num_cus * kHufGridPerCu;  // a persistent grid (3 per CU) is +11 %
     if (grid > cap) grid = cap;
     if (grid < 1) return hipSuccess;
-    if (adaptive)
-        hipLaunchKernelGGL(huffman_from_pixels_kernel<true>, dim3((unsigned)grid), dim3(kHufThreads), 0, stream, es, dev,
-                           bits);
-    else
-        hipLaunchKernelGGL(huffman_from_pixels_kernel<false>, dim3((unsigned)grid), dim3(kHufThreads), 0, stream, es,
-                           dev, bits);
+    with_bools(
+        [&](auto a) {
+            hipLaunchKernelGGL(huffman_from_pixels_kernel<a>, dim3((unsigned)grid), dim3(kHufThreads), 0, stream, es, dev,
+                               bits);
+        },
+        adaptive != 0);
     return hipGetLastError();
 }
 

@@ -115,7 +115,7 @@ __device__ __forceinline__ void aan8t_f(float &v0, float &v1, float &v2, float &
     v7 = ga0 - gb0;
 }
 
-// The fp32 inverse (non-adaptive plans admitted by api.hip inverse_f32_bound:
+// The fp32 inverse (non-adaptive plans admitted by plan_tables.hip inverse_f32_bound:
 // |recon - reference| <= 5e-5 for every input block, e.g. q <= 71 of the standard
 // table; their dequantisation is the reference's q * (1/Q), src/quantization.c:139,
 // 144), in inverse_half's paired-lane layout (lane (h, j): rows 4h..4h+3 of block j):

@@ -93,7 +93,7 @@ __device__ __forceinline__ void stage_store(const u4p (&val)[8], int lane, char 
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)d);
     dst = reinterpret_cast<char *>(((uint64_t)hi << 32) | (uint64_t)lo);
     nbytes = (uint32_t)__builtin_amdgcn_readfirstlane(nbytes);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(dst, (short)0, (int)nbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(dst, (short)0, (int)nbytes, kRsrcFlags);
 #pragma unroll
     for (int k = 0; k < 8; ++k) __builtin_amdgcn_raw_buffer_store_b128(val[k], rs, lane * 16, k * 1024, kNtAux);
 }

@@ -1,5 +1,5 @@
 // dct_amd/csrc/plan.h -- the plan object and the argument helpers shared by the
-// product C-ABI (api.hip) and the diagnostic library's entry points (diag.hip).
+// product C-ABI (api.hip, plan_tables.hip) and the diagnostic library's entry points (diag.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,7 +28,7 @@ int plane_inputs(const dctq_plane *planes, int nplanes, PlaneSet *ps);
 // plane_inputs plus the per-plane coefficient (and optional var_num) outputs
 int plane_set(const dctq_plane *planes, int nplanes, int16_t *const *coef, int32_t *const *var_num, PlaneSet *ps);
 void fill_fast_tables(const double *q, int adaptive, FastTables *t);
-// quantized DC of every constant block, in the reference's operation order (api.hip)
+// quantized DC of every constant block, in the reference's operation order (plan_tables.hip)
 void dc_const_table(const double *d, const double *q, int16_t *tab);
 // rigorous bound of |recon - reference| of the fused round trip's fp32 inverse for the
 // plan's tables (non-adaptive dequantisation; tools/inv_bound.py, idct8_bound.h)
@@ -38,10 +38,8 @@ double inverse_f32_bound(const DevTables &t);
 // divisors Q (2 - nv) >= Q; the DC keeps Q)
 int max_abs_quantized(const DevTables &t);
 }  // namespace dctq
-// the admission tolerance of that bound (== idct8_bound.h kInvTol; api.hip checks they agree)
+// the admission tolerance of that bound (== idct8_bound.h kInvTol; plan_tables.hip checks they agree)
 constexpr double kInvTolDiag = 5e-5;
-namespace dctq {
-}  // namespace dctq
 
 #define HIPCHK(call, what)                                               \
     do {                                                                 \

@@ -10,7 +10,7 @@
 //   W = 4 (uint32): (uint16)value | run << 16 -- any int16 value;
 //   W = 2 (uint16): (run & 63) << 10 | (value & 0x3FF) -- |value| <= 511, which a
 //         plan guarantees when its Q table bounds every quantized coefficient there
-//         (api.hip symbol_bytes; q <= 90 of the standard table): 2 B per symbol,
+//         (plan_tables.hip symbol_bytes; q <= 90 of the standard table): 2 B per symbol,
 //         so dense noise's 45.7 symbols per block take 91 B instead of 183 B --
 //         less than the 128 B of int16 coefficients they shrink.
 //         Runs are 0..63 except in the one symbol of an all-zero block, (0, 64),
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(kRleThreads) void rle_count_kernel(const int16_t *_
         const long long r = nblk - tt * 64;
         const int nb = r < 64 ? (int)r : 64;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<int16_t *>(coef) + tt * 64 * 64, (short)0, nb * 128, 0x00020000);  // past the tail: zeros
+            const_cast<int16_t *>(coef) + tt * 64 * 64, (short)0, nb * 128, kRsrcFlags);  // past the tail: zeros
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, k * 1024, kCountPolicy);
@@ -216,7 +216,7 @@ __device__ __forceinline__ int tile_blocks(long long t, long long nblk) {
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const int16_t *coef, long long t, int nb) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<int16_t *>(coef) + (nb ? t * 64 * 64 : 0), (short)0, nb * 128,
-                                             0x00020000);
+                                             kRsrcFlags);
 }
 
 typedef uint32_t u4r __attribute__((ext_vector_type(4)));
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(kRleThreads, 4) void rle_emit_kernel(const int16_t 
     const uint32_t upto_lo = (uint32_t)upto, upto_hi = (uint32_t)(upto >> 32);
     const long long noffs = nblk + 1;  // offsets[nblk] = end of the last block's symbols
     const __amdgpu_buffer_rsrc_t roff = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint32_t *>(offsets), (short)0, (int)(noffs * 4 < 0x7FFFFFFF ? noffs * 4 : 0x7FFFFFFF), 0x00020000);
+        const_cast<uint32_t *>(offsets), (short)0, (int)(noffs * 4 < 0x7FFFFFFF ? noffs * 4 : 0x7FFFFFFF), kRsrcFlags);
     long long t = (long long)blockIdx.x * kRleWaves + wv;
     if (t >= ntiles) return;
     u4r nq[8];
@@ -314,7 +314,7 @@ __global__ __launch_bounds__(kRleThreads, 4) void rle_emit_kernel(const int16_t 
     // chunk k*64 + lane of the tile = block 8k + lane/8, bytes 16*(lane%8) of its row
     const uint32_t wr = (uint32_t)(lane >> 3) * kEmitPitch + 16u * (lane & 7);
     for (; t < ntiles; t += stride) {
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this tile's loads and the previous tile's stores
+        retire_stores();  // vmcnt(0): this tile's loads and the previous tile's stores
         const uint32_t offv = noff;
         const uint32_t o0 = __builtin_amdgcn_readlane(offv, 0);
         const uint32_t nsym = __builtin_amdgcn_readfirstlane(nend) - o0;
@@ -342,9 +342,9 @@ __global__ __launch_bounds__(kRleThreads, 4) void rle_emit_kernel(const int16_t 
             const uint32_t end = (uint32_t)(cap < pad + nsym ? cap : pad + nsym);      // units [pad, end) land
             uint16_t *base16 = reinterpret_cast<uint16_t *>(symbols) + first;
             const __amdgpu_buffer_rsrc_t rfull =
-                __builtin_amdgcn_make_buffer_rsrc(base16, (short)0, (int)((end & ~1u) * 2u), 0x00020000);
+                __builtin_amdgcn_make_buffer_rsrc(base16, (short)0, (int)((end & ~1u) * 2u), kRsrcFlags);
             const __amdgpu_buffer_rsrc_t redge = __builtin_amdgcn_make_buffer_rsrc(base16, (short)0, (int)(end * 2u),
-                                                                                  0x00020000);
+                                                                                  kRsrcFlags);
             const bool head = pad && end > 1u, tail = (end & 1u) && end - 1u >= pad;  // wave-uniform
             const uint16_t *l16 = reinterpret_cast<const uint16_t *>(lt);
             const uint32_t uhead = head ? l16[1] : 0u, utail = tail ? l16[end - 1u] : 0u;
@@ -352,7 +352,7 @@ __global__ __launch_bounds__(kRleThreads, 4) void rle_emit_kernel(const int16_t 
 #pragma unroll
             for (int r = 0; r < (int)((kLaneWalkMax2 / 2 + 1 + 1023) / 1024); ++r) {
                 if (r * 1024 >= (int)ndw) break;
-                if (r) __builtin_amdgcn_s_waitcnt(0x0F70);
+                if (r) retire_stores();
                 uint32_t v[kMaxChunks];
 #pragma unroll
                 for (int j = 0; j < kMaxChunks; ++j)
@@ -379,14 +379,14 @@ __global__ __launch_bounds__(kRleThreads, 4) void rle_emit_kernel(const int16_t 
             wave_sync_lds();
             const uint32_t nrec = (uint32_t)(room < nsym ? room : nsym) * 4u;
             const __amdgpu_buffer_rsrc_t rsym = __builtin_amdgcn_make_buffer_rsrc(
-                reinterpret_cast<uint32_t *>(symbols) + o0, (short)0, (int)nrec, 0x00020000);
+                reinterpret_cast<uint32_t *>(symbols) + o0, (short)0, (int)nrec, kRsrcFlags);
             // all LDS reads of a round first, then its stores (store-data hazard):
             // chunks of 64 symbols in guarded groups of 4, the tail clipped by num_records;
             // a second round (past 1 024 symbols) starts after a vmcnt(0)
 #pragma unroll
             for (int r = 0; r < (int)((kLaneWalkMax + 1023) / 1024); ++r) {
                 if (r * 1024 >= (int)nsym) break;
-                if (r) __builtin_amdgcn_s_waitcnt(0x0F70);
+                if (r) retire_stores();
                 uint32_t v[kMaxChunks];
 #pragma unroll
                 for (int j = 0; j < kMaxChunks; ++j)
@@ -409,7 +409,7 @@ __global__ __launch_bounds__(kRleThreads, 4) void rle_emit_kernel(const int16_t 
                    ((uint32_t)*reinterpret_cast<const uint16_t *>(lt + (2 * u + 1) * kEmitPitch + zoff) << 16);
         const __amdgpu_buffer_rsrc_t rsym = __builtin_amdgcn_make_buffer_rsrc(
             reinterpret_cast<char *>(symbols) + o0 * (unsigned long long)W, (short)0,
-            (int)((room < 4096ull ? room : 4096ull) * W), 0x00020000);
+            (int)((room < 4096ull ? room : 4096ull) * W), kRsrcFlags);
 #pragma unroll
         for (int u = 0; u < 64; ++u) {
             const uint32_t val = (u & 1) ? z[u >> 1] >> 16 : z[u >> 1] & 0xFFFFu;
@@ -523,7 +523,7 @@ __global__ __launch_bounds__(kRleThreads, W == 4 ? 8 : 7) void rle_decode_kernel
             if (lane_path) {
                 const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc(
                     const_cast<char *>(reinterpret_cast<const char *>(symbols)) + (unsigned long long)s0 * W, (short)0,
-                    (int)(nh * W), 0x00020000);
+                    (int)(nh * W), kRsrcFlags);
                 uint32_t v[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {  // past nh: clipped to 0, no traffic
@@ -536,7 +536,7 @@ __global__ __launch_bounds__(kRleThreads, W == 4 ? 8 : 7) void rle_decode_kernel
                 const uint32_t my_off = (uint32_t)__shfl((int)offv, (lane + h) & 63);
                 const uint32_t my_cnt = (uint32_t)__shfl((int)cnt_lane, (lane + h) & 63);
                 // vmcnt(0): these loads, and the previous half's stores before any LDS read (store-data hazard)
-                __builtin_amdgcn_s_waitcnt(0x0F70);
+                retire_stores();
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     if (j < 3 || lane < 48) lsym[j * 64 + lane] = v[j];
@@ -563,7 +563,7 @@ __global__ __launch_bounds__(kRleThreads, W == 4 ? 8 : 7) void rle_decode_kernel
                 const uint32_t pad = W == 2 ? (s0 & 1u) : 0u;
                 const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc(
                     const_cast<char *>(reinterpret_cast<const char *>(symbols)) + (unsigned long long)(s0 - pad) * W,
-                    (short)0, (int)(W == 4 ? nh * 4u : ((pad + nh + 1u) & ~1u) * 2u), 0x00020000);
+                    (short)0, (int)(W == 4 ? nh * 4u : ((pad + nh + 1u) & ~1u) * 2u), kRsrcFlags);
                 const uint32_t my_off = (uint32_t)__shfl((int)offv, (lane + h) & 63);
                 const uint32_t my_cnt = (uint32_t)__shfl((int)cnt_lane, (lane + h) & 63);
                 const uint32_t cnt = lane < he - h ? (my_cnt < 64u ? my_cnt : 64u) : 0u;
@@ -601,7 +601,7 @@ __global__ __launch_bounds__(kRleThreads, W == 4 ? 8 : 7) void rle_decode_kernel
                 load_batch(0, cur);
                 // vmcnt(0) before any LDS read into registers: the previous half's stores
                 // (store-data hazard); the walk's own loads are in the same count
-                __builtin_amdgcn_s_waitcnt(0x0F70);
+                retire_stores();
 #pragma unroll
                 for (int k = 0; k < 5; ++k)
                     if (k < 4 || lane < 32) reinterpret_cast<u4r *>(lt)[k * 64 + lane] = u4r{0u, 0u, 0u, 0u};
@@ -630,7 +630,7 @@ __global__ __launch_bounds__(kRleThreads, W == 4 ? 8 : 7) void rle_decode_kernel
                 const uint32_t pad = W == 2 ? (s0 & 1u) : 0u;  // as the walk path
                 const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc(
                     const_cast<char *>(reinterpret_cast<const char *>(symbols)) + (unsigned long long)(s0 - pad) * W,
-                    (short)0, (int)(W == 4 ? nh * 4u : ((pad + nh + 1u) & ~1u) * 2u), 0x00020000);
+                    (short)0, (int)(W == 4 ? nh * 4u : ((pad + nh + 1u) & ~1u) * 2u), kRsrcFlags);
                 const int r = lane >> 4, s4 = 4 * (lane & 15);
                 auto group_load = [&](int g, u4r &q, uint32_t &cnt) {
                     const int b = h + 4 * g + r;  // this row's block (past `he`: none)
@@ -657,7 +657,7 @@ __global__ __launch_bounds__(kRleThreads, W == 4 ? 8 : 7) void rle_decode_kernel
                 uint32_t cnt;
                 group_load(0, q, cnt);
                 // vmcnt(0) before any LDS read into registers: the previous half's stores (store-data hazard)
-                __builtin_amdgcn_s_waitcnt(0x0F70);
+                retire_stores();
 #pragma unroll
                 for (int k = 0; k < 5; ++k)
                     if (k < 4 || lane < 32) reinterpret_cast<u4r *>(lt)[k * 64 + lane] = u4r{0u, 0u, 0u, 0u};
@@ -691,14 +691,14 @@ __global__ __launch_bounds__(kRleThreads, W == 4 ? 8 : 7) void rle_decode_kernel
                 }
             }
             wave_sync_lds();
-            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the walk's last (clipped) loads before the read-out
+            retire_stores();  // vmcnt(0): the walk's last (clipped) loads before the read-out
             u4r val[4];
             const int pitch = lane_path ? 128 : kDecPitch;
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 val[k] = *reinterpret_cast<const u4r *>(lt + (8 * k + (lane >> 3)) * pitch + 16 * (lane & 7));
             const __amdgpu_buffer_rsrc_t rs =
-                __builtin_amdgcn_make_buffer_rsrc(coef + (b0 + h) * 64, (short)0, (he - h) * 128, 0x00020000);
+                __builtin_amdgcn_make_buffer_rsrc(coef + (b0 + h) * 64, (short)0, (he - h) * 128, kRsrcFlags);
 #pragma unroll
             for (int k = 0; k < 4; ++k) __builtin_amdgcn_raw_buffer_store_b128(val[k], rs, lane * 16, k * 1024, kNtAux);
         }

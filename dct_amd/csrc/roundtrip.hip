@@ -57,8 +57,7 @@ __global__ __launch_bounds__(kThreads, kRtOcc) void roundtrip8(RoundTripSet rt, 
     uint32_t g = blockIdx.x * kWaves + wv;
     uint2 nxt[8];
     prefetch_batch<true, kRtBufRows>(ps, g, lane, nxt);
-    asm volatile("" : "+v"(nxt[0]), "+v"(nxt[1]), "+v"(nxt[2]), "+v"(nxt[3]), "+v"(nxt[4]), "+v"(nxt[5]),
-                 "+v"(nxt[6]), "+v"(nxt[7])::"memory");
+    fence_rows(nxt);
     uint32_t exact_count = 0;
     char *wstage = reinterpret_cast<char *>(stage) + wv * 64 * kPitch2;
     for (; g < nbatch; g += step) {
@@ -112,14 +111,14 @@ __global__ __launch_bounds__(kThreads, kRtOcc) void roundtrip8(RoundTripSet rt, 
         }
         // lanes j / 32+j: var of block j in x, of block 32+j in y
         const auto vv = __builtin_amdgcn_permlane32_swap((uint32_t)var_num, (uint32_t)var_num, false, false);
-        {
+        {  // store_batch<VAR>, spelled out (fdct8_core.h)
             const __amdgpu_buffer_rsrc_t rs =
-                __builtin_amdgcn_make_buffer_rsrc(out.base, (short)0, (int)(nb * 128u), 0x00020000);
+                __builtin_amdgcn_make_buffer_rsrc(out.base, (short)0, (int)(nb * 128u), kRsrcFlags);
 #pragma unroll
             for (int c = 0; c < 8; ++c) __builtin_amdgcn_raw_buffer_store_b128(val[c], rs, lane * 16, c * 1024, kNtAux);
             if (VAR) {
                 const __amdgpu_buffer_rsrc_t rv =
-                    __builtin_amdgcn_make_buffer_rsrc(out.var, (short)0, (int)(nb * 4u), 0x00020000);
+                    __builtin_amdgcn_make_buffer_rsrc(out.var, (short)0, (int)(nb * 4u), kRsrcFlags);
                 __builtin_amdgcn_raw_buffer_store_b32(var_num, rv, lane * 4, 0, kNtAux);
             }
         }
@@ -148,48 +147,18 @@ __global__ __launch_bounds__(kThreads, kRtOcc) void roundtrip8(RoundTripSet rt, 
     }
 }
 
-template <bool A, bool V, bool S>
-static hipError_t launch_rt(const RoundTripSet &rt, const DevTables *dev, unsigned long long *fb, hipStream_t stream,
-                            int num_cus) {
-    static const int per_cu = resident_per_cu(roundtrip8<A, V, S>, kThreads);
-    const uint32_t nbatch = rt.ps.first[rt.ps.n];
-    const uint32_t want = (nbatch + kWaves - 1) / kWaves;
-    const uint32_t cap = (uint32_t)(num_cus * per_cu * kRtGridMult);
-    hipLaunchKernelGGL((roundtrip8<A, V, S>), dim3(want < cap ? want : cap), dim3(kThreads), 0, stream, rt, dev, fb);
-    return hipGetLastError();
-}
-
-template <bool V, bool S>
-static hipError_t launch_rt_f32(const RoundTripSet &rt, const DevTables *dev, unsigned long long *fb,
-                                hipStream_t stream, int num_cus) {
-    static const int per_cu = resident_per_cu(roundtrip8<false, V, S, true>, kThreads);
-    const uint32_t nbatch = rt.ps.first[rt.ps.n];
-    const uint32_t want = (nbatch + kWaves - 1) / kWaves;
-    const uint32_t cap = (uint32_t)(num_cus * per_cu * kRtGridMult);
-    hipLaunchKernelGGL((roundtrip8<false, V, S, true>), dim3(want < cap ? want : cap), dim3(kThreads), 0, stream, rt,
-                       dev, fb);
-    return hipGetLastError();
-}
-
 hipError_t launch_roundtrip(const RoundTripSet &rt, const DevTables *dev, int adaptive, bool inv_f32,
                             unsigned long long *fallbacks, hipStream_t stream, int num_cus) {
-    const bool a = adaptive != 0, v = rt.ps.var[0] != nullptr, s = fallbacks != nullptr;
-    if (inv_f32 && !a) {
-        if (v) return s ? launch_rt_f32<true, true>(rt, dev, fallbacks, stream, num_cus)
-                        : launch_rt_f32<true, false>(rt, dev, fallbacks, stream, num_cus);
-        return s ? launch_rt_f32<false, true>(rt, dev, fallbacks, stream, num_cus)
-                 : launch_rt_f32<false, false>(rt, dev, fallbacks, stream, num_cus);
-    }
-    if (a) {
-        if (v) return s ? launch_rt<true, true, true>(rt, dev, fallbacks, stream, num_cus)
-                        : launch_rt<true, true, false>(rt, dev, fallbacks, stream, num_cus);
-        return s ? launch_rt<true, false, true>(rt, dev, fallbacks, stream, num_cus)
-                 : launch_rt<true, false, false>(rt, dev, fallbacks, stream, num_cus);
-    }
-    if (v) return s ? launch_rt<false, true, true>(rt, dev, fallbacks, stream, num_cus)
-                    : launch_rt<false, true, false>(rt, dev, fallbacks, stream, num_cus);
-    return s ? launch_rt<false, false, true>(rt, dev, fallbacks, stream, num_cus)
-             : launch_rt<false, false, false>(rt, dev, fallbacks, stream, num_cus);
+    return with_bools(
+        [&](auto a, auto v, auto s, auto f32) {
+            if constexpr (a && f32) {
+                return hipErrorInvalidValue;  // never dispatched: the fp32 inverse is the non-adaptive plans'
+            } else {
+                return launch_persistent<roundtrip8<a, v, s, f32>, kThreads, kWaves, kRtGridMult>(
+                    rt.ps.first[rt.ps.n], num_cus, stream, rt, dev, fallbacks);
+            }
+        },
+        adaptive != 0, rt.ps.var[0] != nullptr, fallbacks != nullptr, inv_f32 && !adaptive);
 }
 
 }  // namespace dctq

@@ -68,7 +68,8 @@ def test_no_runtime_knobs_in_product():
     csrc = os.path.join(ROOT, "dct_amd", "csrc")
     for f in os.listdir(csrc):
         assert "getenv" not in open(os.path.join(csrc, f)).read(), f
-    product = ["fdct8.hip", "roundtrip.hip", "encode.hip", "rle.hip", "huffman.hip", "api.hip", "legacy.hip",
+    product = ["fdct8.hip", "roundtrip.hip", "encode.hip", "rle.hip", "huffman.hip", "decode.hip", "api.hip",
+               "plan_tables.hip", "isolation.hip", "legacy.hip",
                "f64_pair.hip", "fdct8_aux.hip", "fdct8_core.h", "pair_core.h", "scan_core.h", "dctq_internal.h",
                "plan.h", "aan_f64.h", "zigzag.h", "host_tables.h"]
     for f in product:

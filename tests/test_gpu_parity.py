@@ -1135,7 +1135,7 @@ def _basis_sign_blocks():
 
 def test_round_trip_inverse_fp32_within_bound(T, dm):
     """The fused round trip's fp32 inverse (roundtrip8_f32): a non-adaptive plan runs
-    it only when the rigorous bound of tools/inv_bound.py (api.hip
+    it only when the rigorous bound of tools/inv_bound.py (plan_tables.hip
     inverse_f32_bound) keeps |recon - reference| <= 5e-5 for every input block
     (q <= 71 of the standard table).  On blocks that maximise each coefficient, noise,
     extremes, flat and smooth planes: coefficients bit-exact in both inverses, the
@@ -2028,3 +2028,82 @@ def test_randomized_sweep_all_planes_apis(T, dm):
         assert all(np.array_equal(c.cpu().numpy(), wv) for c, wv in zip(ecoefs, want)), ("encode coef", trial)
         assert np.array_equal(off.cpu().numpy().view(np.uint32), woff), ("encode offsets", trial, q, ad)
         assert np.array_equal(_sym32(sym), wsym), ("encode symbols", trial, q, ad)
+
+
+def test_every_dispatch_leaf(T, dm):
+    """Every leaf of the launchers' bool dispatch (adaptive x var_num x fallback counter, the fp32 /
+    fp64 inverse, decode8's three kernels, both adaptive settings of dctq_inverse, the encoder and
+    the Huffman size from pixels), each against the oracle, on two planes in one call: 65 blocks
+    (a full 64-block batch, a one-block tail, two full and a one-block 32-block batch) and 1 block
+    (a plane switch).  Seeded uniform noise of a quarter of the u8 range: block variances of
+    150-400, so an adaptive plan scales every block differently and never as a non-adaptive one
+    (full-range noise has variance > 1000, where the adaptive divisor is Q again).  The DC keeps Q
+    in every plan and is sum(px - 128) / (8 Q00): the blocks where that lies within 1e-9 of a half
+    integer are inside every guard band (>= 2^-25 wide, fill_fast_tables), so the fallback counter
+    must count them (tie flags of other coefficients on top)."""
+    import oracle as O
+    rng = np.random.default_rng(808)
+    hosts = [rng.integers(96, 160, size=(40, 104), dtype=np.uint8), rng.integers(96, 160, size=(8, 8), dtype=np.uint8)]
+    planes = [gpu_px(T, p) for p in hosts]
+    shapes = [p.shape for p in hosts]
+    var = [O.plane_variance(p) for p in hosts]
+    sums = np.concatenate([p.astype(np.int64).reshape(h // 8, 8, w // 8, 8).sum(axis=(1, 3)).ravel() - 64 * 128
+                           for p, (h, w) in zip(hosts, shapes)])
+    q32, q64 = 50, 90
+    assert dm.inverse_bound(q32, 0)[1] is True and dm.inverse_bound(q64, 0)[1] is False
+    for q in (q32, q64):
+        dc = np.abs(sums / 8.0 / O.quant_matrix(8, q)[0, 0])
+        dc_ties = int((np.abs(dc - np.floor(dc) - 0.5) < 1e-9).sum())
+        for ad in (0, 1):
+            plan = dm.Plan(q, ad)
+            want_c = [O.forward_plane(p, q, ad) for p in hosts]
+            want_r = [O.inverse_plane(c, q, ad, v if ad else None) + 128.0 for c, v in zip(want_c, var)]
+            if ad:
+                assert not np.array_equal(want_c[0], O.forward_plane(hosts[0], q, 0))  # the leaves differ
+            counts, recon = {}, None
+            for with_var in (True, False):
+                for with_cnt in (True, False):
+                    cnt = T.zeros(1, dtype=T.int64, device="cuda")
+                    plan.set_fallback_counter(cnt if with_cnt else None)
+                    leaf = (q, ad, with_var, with_cnt)
+                    for fused in (False, True):
+                        vns = [T.full((p.size // 64,), -1, dtype=T.int32, device="cuda") for p in hosts] if with_var else None
+                        if fused:
+                            coefs, recs = plan.round_trip_planes(planes, var_nums=vns)
+                        else:
+                            coefs, recs = plan.forward_quant_planes(planes, var_nums=vns), None
+                        for k in range(2):
+                            assert np.array_equal(coefs[k].cpu().numpy(), want_c[k]), (leaf, fused, k)
+                            if with_var:
+                                assert np.array_equal(vns[k].cpu().numpy().astype(np.float64) / 4096.0, var[k]), (leaf, fused, k)
+                            if fused:
+                                err = np.abs(recs[k].cpu().numpy().astype(np.float64) - want_r[k]).max()
+                                assert err <= 1e-4, (leaf, k, err)
+                        if fused:
+                            recon = recs
+                        n = int(cnt.item())
+                        cnt.zero_()
+                        if with_cnt:
+                            counts[(with_var, fused)] = n
+                        else:
+                            assert n == 0, leaf
+                    plan.set_fallback_counter(None)
+            assert counts[(True, False)] == counts[(False, False)] >= dc_ties, (q, ad, counts, dc_ties)
+            assert counts[(True, True)] == counts[(False, True)] >= dc_ties, (q, ad, counts, dc_ties)
+            # decode8: <adaptive>, <fp32 inverse>, <fp64 inverse> -- the rounded, clamped recon
+            gc = [T.from_numpy(c).cuda() for c in want_c]
+            gv = [T.from_numpy((v * 4096.0).astype(np.int32)).cuda() for v in var]
+            pix = plan.decode_planes(gc, shapes=shapes, var_nums=gv if ad else None)
+            for k, (h, w) in enumerate(shapes):
+                expect = T.round(recon[k].clamp(0, 255)).to(T.uint8).reshape(h // 8, w // 8, 8, 8)
+                assert T.equal(pix[k][0], expect.permute(0, 2, 1, 3).reshape(h, w)), (q, ad, k)
+            # idct8_pair, encode_count_kernel, huffman_from_pixels_kernel: the 65-block plane
+            rec = plan.inverse(gc[0], var_num=gv[0] if ad else None).cpu().numpy().astype(np.float64)
+            assert np.abs(rec - want_r[0]).max() <= 1e-4, (q, ad)
+            (ec,), off, sym = plan.encode_planes(planes[:1])
+            woff, wsym = O.rle_encode_plane(want_c[0])
+            assert np.array_equal(ec.cpu().numpy(), want_c[0]), (q, ad)
+            assert np.array_equal(off.cpu().numpy().view(np.uint32), woff), (q, ad)
+            assert np.array_equal(_sym32(sym), wsym), (q, ad)
+            bits = plan.huffman_bits_planes(planes[:1]).cpu().numpy().view(np.uint32)
+            assert np.array_equal(bits, O.huffman_bits_plane(want_c[0])), (q, ad)

@@ -4,7 +4,7 @@ fp32 inverse (roundtrip8_f32).
 tools/inv_bound.py tracks the kernel's inverse (fp32 scale, the transposed AAN
 graph over columns then rows, + 128) as linear forms with rounding bounds that
 are linear in the per-coefficient input magnitudes, and generates
-dct_amd/csrc/idct8_bound.h; api.hip evaluates it per plan.  Here:
+dct_amd/csrc/idct8_bound.h; plan_tables.hip evaluates it per plan.  Here:
   * the committed header is exactly the generator's output;
   * the library's per-plan bound (host-only diag entry point) equals the
     generator's for every standard quality, and admits exactly q <= 71;

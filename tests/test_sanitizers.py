@@ -55,7 +55,7 @@ def test_c_hosts_build_with_sanitizers(tmp_path):
                  "-o", str(tmp_path / src[:-2])])
 
 
-@pytest.mark.parametrize("src", ["api.hip", "legacy.hip", "diag.hip"])
+@pytest.mark.parametrize("src", ["api.hip", "plan_tables.hip", "isolation.hip", "legacy.hip", "diag.hip"])
 def test_library_host_code_builds_with_sanitizers(src, tmp_path):
     csrc = os.path.join(ROOT, "dct_amd", "csrc")
     run(["hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", "-fPIC", "-ffp-contract=off",

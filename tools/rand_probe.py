@@ -6,7 +6,7 @@ For each step: srand(1), the operation, a device synchronize and a short sleep,
 then one rand() -- its index in glibc's seed-1 sequence is how many draws the
 operation (or a runtime thread it started) consumed.  The library's own calls
 are shown with and without a fresh stream.  Evidence for LaunchIsolation
-(dct_amd/csrc/api.hip) and for the stream tests of tests/test_gpu_parity.py.
+(dct_amd/csrc/isolation.hip) and for the stream tests of tests/test_gpu_parity.py.
 """
 import ctypes as C
 import os
