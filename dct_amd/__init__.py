@@ -51,6 +51,7 @@ def _bind(L: C.CDLL, diagnostic: bool) -> C.CDLL:
         "dctq_forward_float": ([vp, C.POINTER(_Plane), vp, vp], i),
         "dctq_inverse": ([vp, vp, vp, ll, vp, vp], i),
         "dctq_decode_planes": ([vp, vp, vp, C.POINTER(_Plane), i, vp], i),
+        "dctq_decode_symbols_planes": ([vp, vp, i, vp, vp, C.POINTER(_Plane), i, vp], i),
         "dctq_synth": ([C.c_uint64, i, C.POINTER(_Plane), vp], i),
         "dctq_error_string": ([i], C.c_char_p),
         "dctq_synchronize": ([vp], i),
@@ -171,6 +172,35 @@ def _need_planes(outs, var_nums, recons, nbs, planes):
             raise DctqError(f"{name} needs one tensor per plane ({len(nbs)}), got {len(ts)}")
         for k, (t, nb, px) in enumerate(zip(ts, nbs, planes)):
             _need(t, nb * per, dt, f"{name}[{k}]", px.device)
+
+
+def _decode_outs(what, n, shapes, outs, var_nums, devices):
+    """The destination planes of decode_planes / decode_symbols: (outs, descs, nbs).  shapes[k]
+    is (F, H, W) or (H, W); outs[k], if given, a u8 tensor [F, H, W] or [H, W], possibly a
+    strided view; one of the two is needed, and both must agree.  var_nums[k], if given, is
+    sized for plane k's blocks.  devices[k]: where outs[k] is allocated."""
+    import torch
+    if shapes is None and outs is None:
+        raise DctqError(f"{what} needs shapes or outs")
+    for name, ts in (("shapes", shapes), ("outs", outs), ("var_nums", var_nums)):
+        if ts is not None and len(ts) != n:
+            raise DctqError(f"{name} needs one entry per plane ({n}), got {len(ts)}")
+    if shapes is not None:
+        shapes = [(1, *map(int, s)) if len(s) == 2 else tuple(map(int, s)) for s in shapes]
+        if any(len(s) != 3 for s in shapes):
+            raise DctqError("shapes entries must be (F, H, W) or (H, W)")
+    if outs is None:
+        outs = [torch.empty(s, dtype=torch.uint8, device=d) for s, d in zip(shapes, devices)]
+    descs = (_Plane * n)(*[plane_desc(o) for o in outs])
+    nbs = [d.nframes * (d.width // 8) * (d.height // 8) for d in descs]
+    for k, (d, o) in enumerate(zip(descs, outs)):
+        if shapes is not None and (d.nframes, d.height, d.width) != shapes[k]:
+            raise DctqError(f"outs[{k}] is {tuple(o.shape)}, shapes[{k}] says {shapes[k]}")
+        if d.width % 8 or d.height % 8:
+            raise DctqError(f"outs[{k}]: width and height must be multiples of 8")
+        if var_nums is not None:
+            _need(var_nums[k], nbs[k], torch.int32, f"var_nums[{k}]", o.device)
+    return outs, descs, nbs
 
 
 class Plan:
@@ -403,33 +433,43 @@ class Plan:
         needed.  Returns the list of u8 tensors [F, H, W] (outs as given), each pixel
         rne(clamp(r, 0, 255)) of the fp32 recon r that round_trip_planes reports."""
         import torch
+        outs, descs, nbs = _decode_outs("decode_planes", len(coefs), shapes, outs, var_nums,
+                                        [c.device for c in coefs])
         n = len(coefs)
-        if shapes is None and outs is None:
-            raise DctqError("decode_planes needs shapes or outs")
-        for name, ts in (("shapes", shapes), ("outs", outs), ("var_nums", var_nums)):
-            if ts is not None and len(ts) != n:
-                raise DctqError(f"{name} needs one entry per plane ({n}), got {len(ts)}")
-        if shapes is not None:
-            shapes = [(1, *map(int, s)) if len(s) == 2 else tuple(map(int, s)) for s in shapes]
-            if any(len(s) != 3 for s in shapes):
-                raise DctqError("shapes entries must be (F, H, W) or (H, W)")
-        if outs is None:
-            outs = [torch.empty(s, dtype=torch.uint8, device=c.device) for s, c in zip(shapes, coefs)]
-        descs = (_Plane * n)(*[plane_desc(o) for o in outs])
-        nbs = [d.nframes * (d.width // 8) * (d.height // 8) for d in descs]
-        for k, (d, o, c) in enumerate(zip(descs, outs, coefs)):
-            if shapes is not None and (d.nframes, d.height, d.width) != shapes[k]:
-                raise DctqError(f"outs[{k}] is {tuple(o.shape)}, shapes[{k}] says {shapes[k]}")
-            if d.width % 8 or d.height % 8:
-                raise DctqError(f"outs[{k}]: width and height must be multiples of 8")
+        for k, (o, c) in enumerate(zip(outs, coefs)):
             _need(c, nbs[k] * 64, torch.int16, f"coefs[{k}]", o.device)
-            if var_nums is not None:
-                _need(var_nums[k], nbs[k], torch.int32, f"var_nums[{k}]", o.device)
         cp = (C.c_void_p * n)(*[c.data_ptr() for c in coefs])
         vp = (C.c_void_p * n)(*[v.data_ptr() for v in var_nums]) if var_nums is not None else None
         self._chk(self._L.dctq_decode_planes(self._h, C.cast(cp, C.c_void_p),
                                              C.cast(vp, C.c_void_p) if vp is not None else None, descs, n,
                                              _stream_ptr(stream)))
+        return outs
+
+    def decode_symbols(self, symbols, offsets, shapes=None, outs=None, var_nums=None, stream=None):
+        """Run-length symbols -> u8 pixels of up to 4 planes in ONE launch, with no
+        coefficient buffer (dctq_decode_symbols_planes): bit for bit
+        decode_planes(split(rle_decode(symbols, offsets)), ...).  symbols / offsets as
+        encode_planes returns them (blocks numbered plane by plane; offsets int32
+        [sum(nblk_k) + 1]); symbols.dtype picks the format (int16: 2-byte, int32: 4-byte),
+        whatever the plan's own symbol_bytes.  shapes / outs / var_nums as decode_planes."""
+        import torch
+        if not isinstance(symbols, torch.Tensor) or not symbols.is_cuda or symbols.dtype not in (torch.int16, torch.int32):
+            raise DctqError("symbols must be an int16 or int32 tensor on a HIP device")
+        if not symbols.is_contiguous():
+            raise DctqError("symbols must be contiguous")
+        n = len(shapes if shapes is not None else outs if outs is not None else ())
+        outs, descs, nbs = _decode_outs("decode_symbols", n, shapes, outs, var_nums, [symbols.device] * n)
+        if (not isinstance(offsets, torch.Tensor) or not offsets.is_cuda or offsets.dtype != torch.int32
+                or not offsets.is_contiguous() or offsets.numel() != sum(nbs) + 1):
+            raise DctqError(f"offsets must be a contiguous int32 device tensor of {sum(nbs) + 1} elements "
+                            "(one per block of every plane, plus one)")
+        if offsets.device != symbols.device or any(o.device != symbols.device for o in outs):
+            raise DctqError("symbols, offsets and outs must be on one device")
+        vp = (C.c_void_p * n)(*[v.data_ptr() for v in var_nums]) if var_nums is not None else None
+        self._chk(self._L.dctq_decode_symbols_planes(
+            self._h, C.c_void_p(symbols.data_ptr()), 2 if symbols.dtype == torch.int16 else 4,
+            C.c_void_p(offsets.data_ptr()), C.cast(vp, C.c_void_p) if vp is not None else None, descs, n,
+            _stream_ptr(stream)))
         return outs
 
     def decode(self, coef, shape=None, out=None, var_num=None, stream=None):

@@ -70,15 +70,19 @@ static void plane_batches(const dctq::PlaneArgs *pl, int nplanes, int per, uint3
 
 // blk_first[k] = plane k's first block in the concatenated numbering; blk_first[n] = their
 // total, which must stay below `limit`
-static int number_blocks(dctq::EncodeSet *es, long long limit, const char *too_many) {
+static int number_blocks(const dctq::PlaneArgs *pl, int n, uint32_t (&blk_first)[dctq::kMaxPlanes + 1], long long limit,
+                         const char *too_many) {
     long long blocks = 0;
-    for (int k = 0; k < es->ps.n; ++k) {
-        es->blk_first[k] = (uint32_t)blocks;
-        blocks += es->ps.pl[k].nblk;
+    for (int k = 0; k < n; ++k) {
+        blk_first[k] = (uint32_t)blocks;
+        blocks += pl[k].nblk;
         if (blocks >= limit) return fail(DCTQ_EINVAL, too_many);
     }
-    es->blk_first[es->ps.n] = (uint32_t)blocks;
+    blk_first[n] = (uint32_t)blocks;
     return DCTQ_OK;
+}
+static int number_blocks(dctq::EncodeSet *es, long long limit, const char *too_many) {
+    return number_blocks(es->ps.pl, es->ps.n, es->blk_first, limit, too_many);
 }
 
 int dctq::plane_inputs(const dctq_plane *planes, int nplanes, dctq::PlaneSet *ps_out) {
@@ -237,6 +241,31 @@ int dctq_decode_planes(const dctq_plan *plan, const int16_t *const *coef, const 
     plane_batches(ds.pl, nplanes, 32, ds.first);
     HIPCHK(dctq::launch_decode(ds, plan->dev, plan->adaptive, plan->inv_f32 != 0, (hipStream_t)stream, plan->num_cus),
            "decode launch");
+    return DCTQ_OK;
+}
+
+int dctq_decode_symbols_planes(const dctq_plan *plan, const void *symbols, int symbol_bytes, const uint32_t *offsets,
+                               const int32_t *const *var_num, const dctq_plane *dst, int nplanes, void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryDecodeSymbolsPlanes);
+    if (int rc = dctq::check_plan(plan)) return rc;
+    if (!symbols || !offsets || !dst) return fail(DCTQ_EINVAL, "symbols/offsets/dst is NULL");
+    if (symbol_bytes != 2 && symbol_bytes != 4) return fail(DCTQ_EINVAL, "symbol_bytes must be 2 or 4");
+    if (((uintptr_t)symbols) % 4 || ((uintptr_t)offsets) % 4) return fail(DCTQ_EINVAL, "symbols/offsets must be 4-byte aligned");
+    if (nplanes < 1 || nplanes > dctq::kMaxPlanes) return fail(DCTQ_EINVAL, "nplanes must be in [1, 4]");
+    if (plan->adaptive && !var_num) return fail(DCTQ_EINVAL, "adaptive decode needs var_num");
+    dctq::SymbolSet ss = {};
+    ss.n = nplanes;
+    for (int k = 0; k < nplanes; ++k) {
+        if (int rc = dctq::plane_args(&dst[k], &ss.pl[k])) return rc;
+        if (plan->adaptive && !var_num[k]) return fail(DCTQ_EINVAL, "adaptive decode needs every var_num[k]");
+        ss.var[k] = plan->adaptive ? var_num[k] : nullptr;
+    }
+    if (int rc = number_blocks(ss.pl, nplanes, ss.blk_first, 1ll << 26, "more than 2^26 - 1 blocks in one decode"))
+        return rc;
+    for (int k = nplanes + 1; k <= dctq::kMaxPlanes; ++k) ss.blk_first[k] = ss.blk_first[nplanes];
+    HIPCHK(dctq::launch_decode_symbols(ss, symbols, symbol_bytes, offsets, plan->dev, plan->adaptive,
+                                       plan->inv_f32 != 0, (hipStream_t)stream, plan->num_cus),
+           "decode_symbols launch");
     return DCTQ_OK;
 }
 

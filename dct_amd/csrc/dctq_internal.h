@@ -46,6 +46,7 @@ enum Entry : int {
     kEntryForwardFloat,
     kEntryInverse,
     kEntryDecodePlanes,
+    kEntryDecodeSymbolsPlanes,
     kEntrySynth,
     kEntryRleCount,
     kEntryRleEmit,
@@ -216,6 +217,15 @@ struct DecodeSet {
     int n;
 };
 
+// The symbol decoder's planes (decode_symbols.hip): pl[k].src is the DESTINATION plane;
+// blocks numbered over the concatenated planes, as the encoder numbers them.
+struct SymbolSet {
+    PlaneArgs pl[kMaxPlanes];
+    const int32_t *var[kMaxPlanes];        // adaptive plans: all set; otherwise unused
+    uint32_t blk_first[kMaxPlanes + 1];    // each plane's first block; blk_first[n..] = total (< 2^26)
+    int n;
+};
+
 // Plane selection over a PlaneSet or a DecodeSet (64- or 32-block batches).
 // Coefficient / var_num pointer of plane k (wave-uniform or not: a select chain, no
 // indexed kernel-argument loads).
@@ -268,6 +278,9 @@ hipError_t launch_roundtrip(const RoundTripSet &rt, const DevTables *dev, int ad
 // dequantize + inverse DCT + 128 + clamp to u8 pixels in the planes of ds (decode.hip)
 hipError_t launch_decode(const DecodeSet &ds, const DevTables *dev, int adaptive, bool inv_f32, hipStream_t stream,
                          int num_cus);
+// run-length symbols -> u8 pixels in the planes of ss, no coefficients in memory (decode_symbols.hip)
+hipError_t launch_decode_symbols(const SymbolSet &ss, const void *symbols, int symbol_bytes, const uint32_t *offsets,
+                                 const DevTables *dev, int adaptive, bool inv_f32, hipStream_t stream, int num_cus);
 // diagnostic: roundtrip8_f32's data movement without arithmetic (fdct8_diag.hip)
 hipError_t launch_roundtrip_movement(const RoundTripSet &rt, hipStream_t stream, int num_cus);
 size_t encode_workspace_bytes(long long nbatch);

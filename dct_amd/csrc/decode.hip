@@ -20,7 +20,7 @@
 // descriptor over the plane (PlaneArgs::span bytes from its first pixel): an address
 // that went wrong drops the write instead of faulting, as load_rows<true> does for
 // reads.  Lanes past the plane's last block store nothing.
-#include "inverse_core.h"
+#include "decode_core.h"
 
 namespace dctq {
 
@@ -43,18 +43,6 @@ __device__ __forceinline__ void prefetch_coefs(const DecodeSet &ds, uint32_t g, 
         rows[r] = make_uint4(t.x, t.y, t.z, t.w);
     }
     if (ADAPTIVE) vn = __builtin_nontemporal_load(var_of(ds, k) + m);
-}
-
-// Four fp32 pixels -> 4 bytes: clamp to [0, 255] (v_med3_f32), round to nearest even
-// (v_rndne_f32), then the conversion of an exact integer (v_cvt_pk_u8_f32 inserts byte
-// k of the word).
-__device__ __forceinline__ uint32_t pack_u8x4(float a, float b, float c, float d) {
-    uint32_t w = 0u;
-    w = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_rintf(__builtin_amdgcn_fmed3f(a, 0.0f, 255.0f)), 0u, w);
-    w = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_rintf(__builtin_amdgcn_fmed3f(b, 0.0f, 255.0f)), 1u, w);
-    w = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_rintf(__builtin_amdgcn_fmed3f(c, 0.0f, 255.0f)), 2u, w);
-    w = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_rintf(__builtin_amdgcn_fmed3f(d, 0.0f, 255.0f)), 3u, w);
-    return w;
 }
 
 template <bool ADAPTIVE, bool INV32>
@@ -84,27 +72,8 @@ __global__ __launch_bounds__(kThreadsP, 4) void decode8(DecodeSet ds, const DevT
         if constexpr (INV32) inverse_half_f32_rows(dev, cur, h, pack);
         else inverse_half_rows<ADAPTIVE>(dev, cur, vn, h, pack);
 
-        // image position of rows 4h..4h+3 of block n (frame, block row, block column)
-        const uint32_t m = valid ? n : 0u;
-        const uint32_t f = fdiv(m, p.div_frame);
-        const uint32_t rem = m - f * (uint32_t)p.nblk_frame;
-        const uint32_t by = fdiv(rem, p.div_bw);
-        const uint32_t bx = rem - by * (uint32_t)p.bw;
-        uint8_t *base = const_cast<uint8_t *>(p.src);
-        if (p.span) {  // kernel argument: wave-uniform.  Every offset inside the plane is < 2^32
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, (int)p.span, kRsrcFlags);
-            const uint32_t st = (uint32_t)p.stride;
-            const uint32_t off = f * (uint32_t)p.frame_stride + (by * 8u + 4u * (uint32_t)h) * st + bx * 8u;
-            if (valid) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) __builtin_amdgcn_raw_buffer_store_b64(pix[r], rs, off + r * st, 0, kNtAux);
-            }
-        } else if (valid) {  // a plane of 4 GiB or more: 64-bit addresses
-            uint8_t *px = base + (long long)f * p.frame_stride + (long long)(by * 8u + 4u * (uint32_t)h) * p.stride +
-                          (long long)bx * 8;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) __builtin_nontemporal_store(pix[r], reinterpret_cast<u2p *>(px + r * p.stride));
-        }
+        // rows 4h..4h+3 of block n, to their image position (decode_core.h)
+        store_pixel_rows(p, n, valid, h, pix);
     }
 }
 

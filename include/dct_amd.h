@@ -165,6 +165,32 @@ int dctq_inverse(const dctq_plan *plan, const int16_t *coef, const int32_t *var_
 int dctq_decode_planes(const dctq_plan *plan, const int16_t *const *coef, const int32_t *const *var_num,
                        const dctq_plane *dst, int nplanes, void *stream);
 
+/* Decoder from symbols: run-length symbols -> u8 pixels in ONE launch, with no
+ * coefficient buffer.  The contract is an equivalence: the pixels are, bit for
+ * bit, what these two calls produce --
+ *   1. dctq_rle_decode (symbol_bytes 4) or dctq_rle_decode16 (symbol_bytes 2) of
+ *      the N blocks into one buffer c;
+ *   2. dctq_decode_planes(plan, {c + 64 * first_k}, var_num, dst, nplanes), where
+ *      first_k is the number of blocks in the planes before plane k
+ * -- including streams whose runs walk past position 63 of a block (those values
+ * are dropped, as the reference's run_length_decode drops them).
+ * Blocks are numbered as dctq_encode_planes numbers them: plane 0 first, then
+ * plane 1, ...; within a plane frame, block row, block column.  N is the total
+ * over the planes, N < 2^26; offsets holds N + 1 entries, offsets[b] the first
+ * symbol of block b.  symbol_bytes 4: uint32_t (uint16_t)value | run << 16;
+ * symbol_bytes 2: uint16_t (run & 63) << 10 | (value & 0x3FF), 0x0000 = (0, 64);
+ * anything else is DCTQ_EINVAL.  The format is the stream's, not the plan's: a
+ * plan whose dctq_plan_symbol_bytes is 4 may decode a 2-byte stream.  symbols
+ * must be 4-byte aligned.
+ * Everything else as dctq_decode_planes: var_num[k] per plane is required for
+ * adaptive plans and ignored (may be NULL) otherwise; dst[k] as every dctq_plane;
+ * bytes outside width x height are not touched.  S + 4 B read (S: the block's
+ * symbols) + 64 B written per block (+ 4 B adaptive), against S + 4 + 128 + 128
+ * + 64 B for the two calls.  Asynchronous on stream; allocates nothing. */
+int dctq_decode_symbols_planes(const dctq_plan *plan, const void *symbols, int symbol_bytes,
+                               const uint32_t *offsets, const int32_t *const *var_num,
+                               const dctq_plane *dst, int nplanes, void *stream);
+
 /* Zigzag + run-length symbols of quantized blocks (the reference's
  * run_length_encode, src/entropy.c:216-256 over block_to_zigzag :158-178, for
  * every block, blocks concatenated in order).  symbol = (uint16_t)value |
