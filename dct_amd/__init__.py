@@ -63,6 +63,7 @@ def _bind(L: C.CDLL, diagnostic: bool) -> C.CDLL:
         "dctq_plan_symbol_bytes": ([vp], i),
         "dctq_huffman_bits": ([vp, ll, vp, vp], i),
         "dctq_huffman_bits_planes": ([vp, C.POINTER(_Plane), i, vp, vp], i),
+        "dctq_distortion_planes": ([vp, C.POINTER(_Plane), i, vp, vp], i),
         "dctq_stream_release": ([vp], i),
     }
     if diagnostic:
@@ -397,6 +398,31 @@ class Plan:
                                                    _stream_ptr(stream)))
         return out
 
+    def distortion_planes(self, planes, out=None, stream=None):
+        """Per-block squared error of the decoded picture straight from up to 4 u8 planes in ONE
+        launch (dctq_distortion_planes; no coefficient, recon or picture buffer): int32 [N],
+        blocks numbered as huffman_bits_planes numbers them, entry b the sum over block b of
+        (px - dec)^2 with dec bit for bit the pixels of
+        decode_planes(forward_quant_planes(planes, var_nums), var_nums)."""
+        import torch
+        n = len(planes)
+        if n == 0:
+            raise DctqError("distortion_planes needs at least one plane")
+        descs = (_Plane * n)(*[plane_desc(px) for px in planes])
+        nb = sum(d.nframes * (d.width // 8) * (d.height // 8) for d in descs)
+        if out is None:
+            out = torch.empty(nb, dtype=torch.int32, device=planes[0].device)
+        _need(out, nb, torch.int32, "out", planes[0].device)
+        self._chk(self._L.dctq_distortion_planes(self._h, descs, n, C.c_void_p(out.data_ptr()),
+                                                 _stream_ptr(stream)))
+        return out
+
+    def rate_distortion_planes(self, planes, stream=None):
+        """(bits, sse) = (huffman_bits_planes(planes), distortion_planes(planes)): both columns
+        of the reference's per-block report (tests/test_entropy.c:300-393), two launches on one
+        stream, pixels in and 4 + 4 B per block out."""
+        return self.huffman_bits_planes(planes, stream=stream), self.distortion_planes(planes, stream=stream)
+
     def forward_float(self, px, out=None, stream=None):
         import torch
         d = plane_desc(px)
@@ -520,6 +546,17 @@ def huffman_bits(coef, out=None, stream=None):
     _need(out, n, torch.int32, "out", coef.device)
     _check(lib().dctq_huffman_bits(C.c_void_p(coef.data_ptr()), n, C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
     return out
+
+
+def psnr_u8(sse_sum, npixels) -> float:
+    """PSNR in dB of a u8 picture from its summed squared error over npixels pixels:
+    10 log10(255^2 npixels / sse_sum), inf for an exact picture.  Plain host arithmetic: reduce
+    Plan.distortion_planes per plane, per frame or over a whole stack, then call this."""
+    import math
+    sse_sum, npixels = float(sse_sum), float(npixels)
+    if sse_sum <= 0.0:
+        return math.inf
+    return 10.0 * math.log10(255.0 * 255.0 * npixels / sse_sum)
 
 
 def rle_decode(symbols, offsets, out=None, stream=None):

@@ -360,6 +360,22 @@ int dctq_huffman_bits_planes(const dctq_plan *plan, const dctq_plane *planes, in
     return DCTQ_OK;
 }
 
+int dctq_distortion_planes(const dctq_plan *plan, const dctq_plane *planes, int nplanes, uint32_t *sse,
+                           void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryDistortionPlanes);
+    if (int rc = dctq::check_plan(plan)) return rc;
+    if (!sse || ((uintptr_t)sse) % 4) return fail(DCTQ_EINVAL, "sse is NULL or not 4-byte aligned");
+    // pixel planes only: no coefficient, var_num or picture buffer (es.ps.coef / var stay NULL)
+    dctq::EncodeSet es = {};
+    int rc = dctq::plane_inputs(planes, nplanes, &es.ps);
+    if (rc) return rc;
+    if ((rc = number_blocks(&es, 1ll << 26, "more than 2^26 - 1 blocks in one launch"))) return rc;
+    HIPCHK(dctq::launch_distortion(es, plan->dev, plan->adaptive, plan->inv_f32 != 0, sse, (hipStream_t)stream,
+                                   plan->num_cus),
+           "distortion launch");
+    return DCTQ_OK;
+}
+
 int dctq_device_count(int *count) {
     DCTQ_ENTRY;
     HIPCHK(hipGetDeviceCount(count), "hipGetDeviceCount");

@@ -54,6 +54,7 @@ enum Entry : int {
     kEntryRleDecode16,
     kEntryHuffmanBits,
     kEntryHuffmanBitsPlanes,
+    kEntryDistortionPlanes,
     kEntrySynchronize,
 };
 static_assert(kEntrySynchronize < 32, "LaunchIsolation keeps one bit per entry point in a uint32_t");
@@ -304,6 +305,9 @@ hipError_t launch_rle_emit(const int16_t *coef, long long nblk, const uint32_t *
 hipError_t launch_huffman_bits(const int16_t *coef, long long nblk, uint32_t *bits, hipStream_t stream, int num_cus);
 hipError_t launch_huffman_from_pixels(const EncodeSet &es, const DevTables *dev, int adaptive, uint32_t *bits,
                                       hipStream_t stream, int num_cus);
+// per-block squared error of the decoded u8 picture against its source, from pixels (distortion.hip)
+hipError_t launch_distortion(const EncodeSet &es, const DevTables *dev, int adaptive, bool inv_f32, uint32_t *sse,
+                             hipStream_t stream, int num_cus);
 hipError_t launch_rle_decode(const void *symbols, int symbol_bytes, const uint32_t *offsets, long long nblk,
                              int16_t *coef, hipStream_t stream, int num_cus);
 // diagnostic library (fdct8_diag.hip): the lane-per-block fp64 kernels (variant 1)

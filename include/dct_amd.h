@@ -233,6 +233,30 @@ int dctq_huffman_bits(const int16_t *coef, long long nblocks, uint32_t *bits, vo
  * never leave the chip.  bits: 4-byte aligned, one entry per block. */
 int dctq_huffman_bits_planes(const dctq_plan *plan, const dctq_plane *planes, int nplanes, uint32_t *bits,
                              void *stream);
+/* Per-block distortion straight from pixels, the other column of the reference's
+ * per-block report (tests/test_entropy.c:300-393: forward -> quantize ->
+ * dequantize -> inverse -> clamp -> squared error), in ONE launch: for block b,
+ *   sse[b] = sum over its 64 pixels of (src - dec)^2,
+ * where dec is, bit for bit, the u8 pixel that dctq_forward_quant_planes(plan,
+ * planes, ..., coef, var_num) followed by dctq_decode_planes(plan, coef, var_num,
+ * dst) writes at that position: dec = (uint8) rne(clamp(r, 0, 255)) of the fp32
+ * recon r of dctq_round_trip_planes (the fp32 inverse where the plan's bound
+ * admits it, fp64 otherwise; adaptive plans use the block's own var_num, which
+ * the caller neither supplies nor receives).  No coefficient, recon or picture
+ * buffer exists: 64 B read and 4 B written per block.  Blocks are numbered as
+ * dctq_huffman_bits_planes numbers them (plane 0 first; within a plane by frame,
+ * block row, block column); their total N must stay below 2^26.  sse[b] <=
+ * 64 * 255^2 = 4 161 600.  sse: 4-byte aligned, N entries.  Asynchronous on
+ * stream; allocates nothing.  DCTQ_EINVAL: a NULL pointer, nplanes outside
+ * 1..4, bad plane geometry, N >= 2^26.
+ * Relation to the reference's PSNR: the reference squares the error of the
+ * clamped but UNROUNDED double c = clamp(recon, 0, 255); this entry point
+ * reports the error of the u8 picture a decoder outputs.  With |dec - c| <=
+ * T = 0.5 + 1e-4 per pixel (rounding plus the recon bound) and e = src - c,
+ *   sum max(|e| - T, 0)^2 <= sse[b] <= sum (|e| + T)^2.
+ * PSNR over any set of blocks: 10 log10(255^2 * 64 * blocks / sum of sse). */
+int dctq_distortion_planes(const dctq_plan *plan, const dctq_plane *planes, int nplanes, uint32_t *sse,
+                           void *stream);
 
 /* The calling thread forgets `stream` (call it before hipStreamDestroy): the
  * library keeps no per-stream device memory, only each thread's list of the
