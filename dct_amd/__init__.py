@@ -435,7 +435,9 @@ class Plan:
         return out
 
     def inverse(self, coef, var_num=None, out=None, stream=None):
-        """int16 [N, 64] -> float32 [N, 64] = dct_inverse(dequantize(coef)) + 128."""
+        """int16 [N, 64] -> float32 [N, 64] = dct_inverse(dequantize(coef)) + 128: fp64, rounded
+        once to fp32 (|err| <= 2^-24 |recon|: below 1e-4 for |recon| < 2048, i.e. for every
+        forward-produced block of a non-adaptive plan, not for arbitrary coefficients)."""
         import torch
         _need(coef, 0, torch.int16, "coef")
         n = coef.numel() // 64
@@ -457,7 +459,11 @@ class Plan:
         [H, W] and may be a strided view (e.g. a padded buffer sliced to width): bytes
         outside width x height of each frame are not touched.  One of shapes / outs is
         needed.  Returns the list of u8 tensors [F, H, W] (outs as given), each pixel
-        rne(clamp(r, 0, 255)) of the fp32 recon r that round_trip_planes reports."""
+        rne(clamp(r, 0, 255)) of the fp32 recon r that round_trip_planes reports.
+        Within 0.5 + 1e-4 of the clamped reference for coefficients inside the plan's
+        forward range (what forward_quant produces from u8 pixels); any other int16 is
+        decoded too, within 0.5 + a bound linear in the block's coefficient magnitudes
+        (include/dct_amd.h, tools/inv_bound.py block_error)."""
         import torch
         outs, descs, nbs = _decode_outs("decode_planes", len(coefs), shapes, outs, var_nums,
                                         [c.device for c in coefs])
@@ -477,7 +483,9 @@ class Plan:
         decode_planes(split(rle_decode(symbols, offsets)), ...).  symbols / offsets as
         encode_planes returns them (blocks numbered plane by plane; offsets int32
         [sum(nblk_k) + 1]); symbols.dtype picks the format (int16: 2-byte, int32: 4-byte),
-        whatever the plan's own symbol_bytes.  shapes / outs / var_nums as decode_planes."""
+        whatever the plan's own symbol_bytes.  shapes / outs / var_nums as decode_planes,
+        and its error bound for the domain the symbols' values fall in (a 4-byte symbol
+        carries any int16, a 2-byte symbol [-512, 511])."""
         import torch
         if not isinstance(symbols, torch.Tensor) or not symbols.is_cuda or symbols.dtype not in (torch.int16, torch.int32):
             raise DctqError("symbols must be an int16 or int32 tensor on a HIP device")
@@ -499,7 +507,7 @@ class Plan:
         return outs
 
     def decode(self, coef, shape=None, out=None, var_num=None, stream=None):
-        """One plane of decode_planes: int16 [nblk, 64] -> u8 [F, H, W]."""
+        """One plane of decode_planes: int16 [nblk, 64] -> u8 [F, H, W] (same bound, per input domain)."""
         return self.decode_planes([coef], None if shape is None else [shape], None if out is None else [out],
                                   None if var_num is None else [var_num], stream)[0]
 

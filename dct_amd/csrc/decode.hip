@@ -5,6 +5,10 @@
 // (inverse_core.h: inverse_half_f32 for plans the fp32 bound admits, the fp64
 // inverse_half<ADAPTIVE> rounded once to fp32 otherwise), i.e. the last arrow of the
 // reference's pipeline tests/test_entropy.c:350-393 (dequantize, dct_inverse, clamp).
+// The fp32 inverse's 5e-5 holds for every block of u8 pixels (coefficients inside the
+// plan's forward range); the coefficients here are the caller's, and outside that range
+// its bound grows linearly with the block's magnitudes (include/dct_amd.h,
+// tools/inv_bound.py block_error; tests/test_decode_foreign_gpu.py).
 //
 // 128 B in + 64 B out per block (+ 4 B of var_num, adaptive plans) against the 384 B
 // of dctq_inverse, whose fp32 block-major recon a host then has to clamp and un-tile.

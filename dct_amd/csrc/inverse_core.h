@@ -116,8 +116,10 @@ __device__ __forceinline__ void aan8t_f(float &v0, float &v1, float &v2, float &
 }
 
 // The fp32 inverse (non-adaptive plans admitted by plan_tables.hip inverse_f32_bound:
-// |recon - reference| <= 5e-5 for every input block, e.g. q <= 71 of the standard
-// table; their dequantisation is the reference's q * (1/Q), src/quantization.c:139,
+// |recon - reference| <= 5e-5 for every block of u8 pixels, e.g. q <= 71 of the standard
+// table; for coefficients outside the plan's forward range, which the decoders accept,
+// the bound grows linearly with the block's magnitudes (tools/inv_bound.py block_error);
+// their dequantisation is the reference's q * (1/Q), src/quantization.c:139,
 // 144), in inverse_half's paired-lane layout (lane (h, j): rows 4h..4h+3 of block j):
 // x_uv = fl32(q_uv * fl32(iscale_uv)) (one v_pk_mul per coefficient pair, the scale
 // pair of the lane's half-wave in SGPRs), the columns (after the exact lane-half

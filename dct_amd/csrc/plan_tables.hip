@@ -81,7 +81,10 @@ void dctq::dc_const_table(const double *d, const double *q, int16_t *tab) {
 
 // The fused round trip's fp32 inverse is admitted for a non-adaptive plan when the
 // rigorous bound of tools/inv_bound.py (idct8_bound.h) keeps |recon - reference|
-// within kInvTol (5e-5, half of north_star's 1e-4) for EVERY input block:
+// within kInvTol (5e-5, half of north_star's 1e-4) for every block of u8 pixels, i.e.
+// every coefficient block inside the plan's forward range (NOT every int16 block a
+// decoder may be handed: outside the range the same bound, evaluated at the block's own
+// magnitudes, grows linearly -- tools/inv_bound.py block_error, include/dct_amd.h):
 // |c_uv| <= 128 L1(D_u) L1(D_v) for centred pixels, so |q_uv| <= round(c_max / Q)
 // and |x_uv| <= B_uv = |q|max * (1/Q) * S_u S_v (the reference's 1/Q dequantisation,
 // src/quantization.c:139,144); per output pixel the bound is G.B (1 + u) + u (128 + |L|.B)

@@ -94,7 +94,9 @@ int dctq_forward_quant_planes(const dctq_plan *plan, const dctq_plane *planes, i
  * dctq_forward_quant_planes, and
  *   recon[k][b][64] = dct_inverse(dequantize(coef[k][b])) + 128
  * exactly as dctq_inverse(plan, coef[k], var_num[k], ...) would produce it
- * (float, unclamped, |err| <= 1e-4).  The quantized ints go from the forward to
+ * (float, unclamped, |err| <= 1e-4: the coefficients here are the forward's own,
+ * of u8 pixels, so they lie in the plan's forward range -- see dctq_decode_planes
+ * -- and |recon| stays below 2048).  The quantized ints go from the forward to
  * the inverse through LDS: 448 B of HBM traffic per block instead of 584 B for
  * the two calls.  var_num is optional even for adaptive plans.  recon 16-byte
  * aligned. */
@@ -139,7 +141,15 @@ int dctq_forward_float(const dctq_plan *plan, const dctq_plane *src, float *coef
 /* Inverse: dequantize (reference semantics incl. the non-adaptive 1/Q
  * multiplier, src/quantization.c:139,144) + dct_inverse + 128, per block:
  *   recon[b][64] = dct_inverse(dequantize(coef[b], var_num[b]/4096)) + 128
- * (float, unclamped; |err| <= 1e-4).  var_num is required when adaptive. */
+ * (float, unclamped), for ANY int16 coefficients and any int32 var_num: computed
+ * in fp64 and rounded once to fp32, so
+ *   |err| <= 2^-24 * |recon| (+ the fp64 arithmetic's own error, below 1e-9 per
+ *   1024 of summed input magnitude),
+ * which is below 1e-4 wherever |recon| < 2048.  That covers every block a
+ * non-adaptive plan's forward produces from u8 pixels; it does not cover
+ * arbitrary coefficients -- int16 values
+ * under an adaptive plan, which multiplies by Q, reach |recon| ~ 1e7, where one
+ * fp32 rounding alone is ~0.5.  var_num is required when adaptive. */
 int dctq_inverse(const dctq_plan *plan, const int16_t *coef, const int32_t *var_num, long long nblocks,
                  float *recon, void *stream);
 
@@ -154,8 +164,27 @@ int dctq_inverse(const dctq_plan *plan, const int16_t *coef, const int32_t *var_
  *   pix = (uint8_t) rne(min(max(r, 0), 255)),  rne = round to nearest, ties to even,
  * where r is the fp32 value dctq_round_trip_planes stores as recon for the same
  * plan and coefficients (so the result equals clamping and rounding that recon,
- * bit for bit); hence |pix - clamp(dct_inverse(dequantize(coef)) + 128, 0, 255)|
- * <= 0.5 + 1e-4 for every pixel.
+ * bit for bit).  Against the reference value c = dct_inverse(dequantize(coef)) + 128:
+ *   |pix - clamp(c, 0, 255)| <= 0.5 + e  for every pixel, and the clamp is exact
+ *   beyond e (pix == 0 where c < -e, pix == 255 where c > 255 + e),
+ * where e depends on the INPUT DOMAIN, since coef is the caller's and a symbol
+ * stream can carry any int16:
+ *   - coefficients within the plan's forward range, |coef_uv| <= round(128 *
+ *     L1(D_u) * L1(D_v) / Q_uv) (D the DCT matrix; what a forward of u8 pixels can
+ *     produce, and the range dctq_plan_symbol_bytes compares with 511): e <= 1e-4
+ *     (5e-5 where the plan decodes through the fp32 inverse);
+ *   - any other int16 input, plans that decode through the fp32 inverse
+ *     (non-adaptive plans whose bound over the forward range is <= 5e-5: q <= 71
+ *     of the standard table): e grows linearly with the block's coefficient
+ *     magnitudes x_k = |coef_k| / Q_k * S_u S_v,
+ *       e_p = (G[p].x)(1 + 2^-24) + 2^-24 (128 + |L[p]|.x) + 1e-9   for pixel p
+ *     (G = kInvErrG, |L| = kInvAbsL of csrc/idct8_bound.h; tools/inv_bound.py
+ *     block_error), up to ~1e-3 for blocks of arbitrary int16 at q50..71;
+ *   - any other int16 input, all other plans (fp64 inverse, one rounding to
+ *     fp32): e = 2^-24 * max(|c|, 128) plus the fp64 error (1e-9 per 1024 of summed
+ *     magnitude), so e <= 1e-4 for every pixel inside [0, 255].
+ * var_num is read as given: any int32 is accepted, var = var_num / 4096 goes
+ * through the reference's clamp min(1, max(0.1, var / 1000)).
  * var_num[k] (per block, as dctq_forward_quant writes it) is required for
  * adaptive plans; non-adaptive plans ignore var_num, which may be NULL.
  * coef[k] 16-byte aligned; dst[k] as every dctq_plane (pixels 8-byte aligned,
@@ -173,7 +202,10 @@ int dctq_decode_planes(const dctq_plan *plan, const int16_t *const *coef, const 
  *   2. dctq_decode_planes(plan, {c + 64 * first_k}, var_num, dst, nplanes), where
  *      first_k is the number of blocks in the planes before plane k
  * -- including streams whose runs walk past position 63 of a block (those values
- * are dropped, as the reference's run_length_decode drops them).
+ * are dropped, as the reference's run_length_decode drops them), and with the
+ * error bound of dctq_decode_planes for the domain the decoded coefficients fall
+ * in: a 4-byte symbol carries any int16, a 2-byte symbol any value in [-512, 511]
+ * (the payload 0x200, which no encoder here emits, is -512).
  * Blocks are numbered as dctq_encode_planes numbers them: plane 0 first, then
  * plane 1, ...; within a plane frame, block row, block column.  N is the total
  * over the planes, N < 2^26; offsets holds N + 1 entries, offsets[b] the first
@@ -252,7 +284,9 @@ int dctq_huffman_bits_planes(const dctq_plan *plan, const dctq_plane *planes, in
  * Relation to the reference's PSNR: the reference squares the error of the
  * clamped but UNROUNDED double c = clamp(recon, 0, 255); this entry point
  * reports the error of the u8 picture a decoder outputs.  With |dec - c| <=
- * T = 0.5 + 1e-4 per pixel (rounding plus the recon bound) and e = src - c,
+ * T = 0.5 + 1e-4 per pixel (rounding plus the recon bound; the coefficients are
+ * this call's own forward of u8 pixels, inside the plan's forward range, so the
+ * bound of dctq_decode_planes holds without condition) and e = src - c,
  *   sum max(|e| - T, 0)^2 <= sse[b] <= sum (|e| + T)^2.
  * PSNR over any set of blocks: 10 log10(255^2 * 64 * blocks / sum of sse). */
 int dctq_distortion_planes(const dctq_plan *plan, const dctq_plane *planes, int nplanes, uint32_t *sse,

@@ -10,7 +10,10 @@ dct_amd/csrc/idct8_bound.h; plan_tables.hip evaluates it per plan.  Here:
     generator's for every standard quality, and admits exactly q <= 71;
   * an fp32 simulation of the kernel's operation sequence on blocks that maximise
     each coefficient (and on noise) stays within the bound against the oracle's
-    fp64 reference inverse (src/dct.c:80-105, src/quantization.c:133-151).
+    fp64 reference inverse (src/dct.c:80-105, src/quantization.c:133-151);
+  * on coefficients outside that range (a decoder's input is the caller's) the same
+    bound at each block's own magnitudes holds, and no constant does.
+The simulation itself is tools/inv_model.py.
 """
 import os
 import sys
@@ -22,6 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import inv_bound as IB  # noqa: E402
 from aan_model import aan8t, scales, C4, C6, C2mC6, C2pC6  # noqa: E402,F401
+import coef_families as CF  # noqa: E402
+from inv_model import F32, kernel_inverse as _kernel_inverse  # noqa: E402,F401
 
 
 @pytest.fixture(scope="module")
@@ -48,34 +53,6 @@ def test_library_bound_equals_generator(GL):
         if a:
             admitted.append(q)
     assert admitted == list(range(1, 72)), admitted
-
-
-class F32:
-    """The kernel's fp32 arithmetic on numpy arrays: every op rounded to fp32
-    (fma: the exact product plus the addend in fp64, then one rounding)."""
-    f = staticmethod(np.float32)
-
-    def add(self, a, b): return (a + b).astype(np.float32)
-    def sub(self, a, b): return (a - b).astype(np.float32)
-    def neg(self, a): return -a
-    def mul(self, a, k): return (a * np.float32(k)).astype(np.float32)
-    def fma(self, k, a, b):
-        return (np.float64(np.float32(k)) * a.astype(np.float64) + b.astype(np.float64)).astype(np.float32)
-
-
-def _kernel_inverse(q, iscale32):
-    """recon of int coefficient blocks q [n, 64] as roundtrip.hip inverse_block_f32 computes it."""
-    A = F32()
-    x = (q.astype(np.float32) * iscale32[None, :]).astype(np.float32)
-    x = [x[:, k] for k in range(64)]
-    for v in range(8):
-        col = aan8t([x[u * 8 + v] for u in range(8)], A)
-        for i in range(8):
-            x[i * 8 + v] = col[i]
-    for i in range(8):
-        row = aan8t(x[i * 8:i * 8 + 8], A)
-        x[i * 8:i * 8 + 8] = row
-    return np.stack([(xx + np.float32(128.0)).astype(np.float32) for xx in x], axis=1)
 
 
 def _basis_sign_blocks():
@@ -105,6 +82,41 @@ def test_fp32_inverse_simulation_within_bound(GL, q):
     bound = IB.plan_error(q, *GL)[0]
     assert err <= bound, (q, err, bound)
     assert bound <= 5e-5
+
+
+@pytest.mark.parametrize("q", [10, 50, 71])
+def test_fp32_inverse_foreign_coefficients(GL, q):
+    """Coefficients no forward produced (tools/coef_families.py: any int16, +-511, multiples
+    of the plan's range, its edge, one-hot, saturated, sparse).  The fp32 inverse's error
+    is bounded by tools/inv_bound.py block_error -- the plan's bound at each block's own
+    magnitudes -- on every block; that bound is within kInvTol = 5e-5 on every block inside
+    the plan's forward range; and the constant 1e-4 does NOT hold outside it (q50, q71 on
+    32768 blocks of uniform int16, seed 7: about 5.5e-4 and 9.2e-4), which is why
+    include/dct_amd.h states the decoders' bound per input domain."""
+    import oracle as O
+    G, L = GL
+    iscale32 = (O.dequant_matrix(O.quant_matrix(8, q)).ravel() * np.outer(scales(), scales()).ravel()).astype(np.float32)
+    qm = CF.qmax(q)
+    assert IB.plan_error(q, G, L)[0] <= 5e-5
+    for name in CF.NAMES:
+        coef = CF.family(name, q)
+        want = O.inverse_plane(coef, q, 0) + 128.0
+        got = _kernel_inverse(coef, iscale32).astype(np.float64)
+        e = IB.block_error(q, coef, G, L)
+        err = np.abs(got - want)
+        inside = (np.abs(coef.astype(np.int32)) <= qm[None, :]).all(axis=1)
+        print(f"q{q} {name}: {int(inside.sum())}/{len(coef)} blocks in range, max err {err.max():.3e}, "
+              f"max err/bound {(err / e).max():.3f}, max bound in range {e[inside].max() if inside.any() else 0.0:.3e}")
+        assert (err <= e).all(), (q, name, float((err / e).max()))
+        assert (e[inside] <= 5e-5).all(), (q, name, float(e[inside].max()))
+    assert CF.family("range_x1", q).shape[0] == int(
+        (np.abs(CF.family("range_x1", q).astype(np.int32)) <= qm[None, :]).all(axis=1).sum())
+    if q in (50, 71):
+        coef = CF.family("int16", q, n=32768, seed=7)
+        err = np.abs(_kernel_inverse(coef, iscale32).astype(np.float64) - (O.inverse_plane(coef, q, 0) + 128.0))
+        print(f"q{q} int16 x 32768: max err {err.max():.3e}")
+        assert err.max() > 1e-4, (q, float(err.max()))
+        assert (err <= IB.block_error(q, coef, G, L)).all()
 
 
 def test_symbol_format_bound():

@@ -123,6 +123,24 @@ def plan_error(q, G, L, tol=5e-5):
     return float(e.max()), float((np.abs(L) @ B).max())
 
 
+def block_magnitudes(coef, dequant):
+    """x_k = |q_k| * dequant_k * S_u S_v per block: the inverse's exact input magnitudes,
+    [n, 64], of int blocks coef [n, 64] under the dequantisation multipliers dequant
+    ([64], or [n, 64] for the per-block multipliers of adaptive plans)."""
+    S = np.array(scales())
+    return np.abs(np.asarray(coef, np.float64)) * np.asarray(dequant, np.float64) * np.outer(S, S).ravel()
+
+
+def block_error(q, coef, G, L):
+    """The bound of plan_error evaluated at each block's ACTUAL magnitudes instead of
+    the plan's forward range: e [n, 64], |fp32 recon - reference| <= e[b, p] for pixel p
+    of block b of ANY int coefficients coef [n, 64] decoded by the non-adaptive plan of
+    quality q.  Linear in the magnitudes, so it is below plan_error for every block
+    inside the forward range and grows in proportion outside it."""
+    x = block_magnitudes(coef, 1.0 / quant_table(q))
+    return (x @ G.T) * (1 + U) + U * (128.0 + x @ np.abs(L).T) + 1e-9
+
+
 def header(G, L):
     fmt = lambda a: ",\n    ".join(", ".join("%.17g" % x for x in row) for row in a)  # noqa: E731
     return f"""// GENERATED by tools/inv_bound.py -- do not edit.
