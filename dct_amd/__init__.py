@@ -60,6 +60,10 @@ def _bind(L: C.CDLL, diagnostic: bool) -> C.CDLL:
         "dctq_rle_emit": ([vp, ll, vp, vp, vp], i),
         "dctq_rle_decode": ([vp, vp, ll, vp, vp], i),
         "dctq_rle_decode16": ([vp, vp, ll, vp, vp], i),
+        "dctq_bits_workspace_bytes": ([ll], C.c_size_t),
+        "dctq_bits_pack": ([vp, i, vp, ll, vp, vp, ll, vp, vp], i),
+        "dctq_bits_decode": ([vp, vp, ll, vp, vp], i),
+        "dctq_decode_bits_planes": ([vp, vp, vp, vp, C.POINTER(_Plane), i, vp], i),
         "dctq_plan_symbol_bytes": ([vp], i),
         "dctq_huffman_bits": ([vp, ll, vp, vp], i),
         "dctq_huffman_bits_planes": ([vp, C.POINTER(_Plane), i, vp, vp], i),
@@ -506,6 +510,38 @@ class Plan:
             _stream_ptr(stream)))
         return outs
 
+    def decode_bits(self, bytes, offsets, shapes=None, outs=None, var_nums=None, stream=None):
+        """The bit-packed stream "bits v1" -> u8 pixels of up to 4 planes in ONE launch, with no
+        coefficient buffer (dctq_decode_bits_planes): bit for bit
+        decode_planes(split(bits_decode(bytes, offsets)), ...).  bytes (uint8) / offsets (int32
+        [sum(nblk_k) + 1], byte offsets) as bits_pack returns them, blocks numbered plane by
+        plane; any bytes decode.  shapes / outs / var_nums as decode_planes, and its error bound
+        for the domain the decoded values fall in (a packed symbol carries any int16)."""
+        import torch
+        if not isinstance(bytes, torch.Tensor) or not bytes.is_cuda or bytes.dtype != torch.uint8:
+            raise DctqError("bytes must be a uint8 tensor on a HIP device")
+        if not bytes.is_contiguous():
+            raise DctqError("bytes must be contiguous")
+        n = len(shapes if shapes is not None else outs if outs is not None else ())
+        outs, descs, nbs = _decode_outs("decode_bits", n, shapes, outs, var_nums, [bytes.device] * n)
+        _need_byte_offsets(offsets, sum(nbs), bytes)
+        if any(o.device != bytes.device for o in outs):
+            raise DctqError("bytes, offsets and outs must be on one device")
+        vp = (C.c_void_p * n)(*[v.data_ptr() for v in var_nums]) if var_nums is not None else None
+        self._chk(self._L.dctq_decode_bits_planes(
+            self._h, C.c_void_p(bytes.data_ptr()), C.c_void_p(offsets.data_ptr()),
+            C.cast(vp, C.c_void_p) if vp is not None else None, descs, n, _stream_ptr(stream)))
+        return outs
+
+    def encode_bits_planes(self, planes, outs=None, capacity=None, stream=None, symbol_bytes=None):
+        """encode_planes + bits_pack: forward, zigzag/RLE and the bit-packed stream of up to 4
+        planes.  Returns (coefs [int16 [nblk_k, 64]], byte_offsets int32 [N+1], bytes uint8
+        [total]); capacity (bytes) defaults to the stream's own size.  The symbols are an
+        intermediate of the plan's most compact format (or symbol_bytes)."""
+        coefs, off, sym = self.encode_planes(planes, outs=outs, stream=stream, symbol_bytes=symbol_bytes)
+        packed, boff = bits_pack(sym, off, capacity=capacity, stream=stream)
+        return coefs, boff, packed
+
     def decode(self, coef, shape=None, out=None, var_num=None, stream=None):
         """One plane of decode_planes: int16 [nblk, 64] -> u8 [F, H, W] (same bound, per input domain)."""
         return self.decode_planes([coef], None if shape is None else [shape], None if out is None else [out],
@@ -578,6 +614,78 @@ def rle_decode(symbols, offsets, out=None, stream=None):
     fn = lib().dctq_rle_decode16 if symbols.dtype == torch.int16 else lib().dctq_rle_decode
     _check(fn(C.c_void_p(symbols.data_ptr()), C.c_void_p(offsets.data_ptr()), n, C.c_void_p(out.data_ptr()),
               _stream_ptr(stream)))
+    return out
+
+
+def _need_byte_offsets(offsets, nblk, bytes):
+    """The offsets of a symbol or packed stream: a contiguous int32 device tensor of nblk + 1
+    elements (nblk None: of any number of blocks), on the device of `bytes`."""
+    import torch
+    if (not isinstance(offsets, torch.Tensor) or not offsets.is_cuda or offsets.dtype != torch.int32
+            or not offsets.is_contiguous() or offsets.numel() < 2
+            or (nblk is not None and offsets.numel() != nblk + 1)):
+        want = "at least 2" if nblk is None else str(nblk + 1)
+        raise DctqError(f"offsets must be a contiguous int32 device tensor of {want} elements "
+                        "(one per block, plus one)")
+    if offsets.device != bytes.device:
+        raise DctqError("bytes and offsets must be on one device")
+
+
+def bits_pack(symbols, offsets, symbol_bytes=None, capacity=None, stream=None):
+    """Run-length symbols -> the bit-packed stream "bits v1" (dctq_bits_pack; the format:
+    include/dct_amd.h, tools/bits_ref.py).  symbols / offsets as encode_planes or rle_encode
+    return them (or anybody's: any int16 value, any run); symbols.dtype picks the format
+    (int16: 2-byte, int32: 4-byte), and symbol_bytes, if given, must agree.  Returns
+    (bytes uint8 [min(total, capacity)], byte_offsets int32 [N+1], uint32 bit patterns,
+    always complete).  capacity None: two passes, the second sized by the first's total;
+    0: the offsets only.  Reads the total back (one sync)."""
+    import torch
+    if not isinstance(symbols, torch.Tensor) or not symbols.is_cuda or symbols.dtype not in (torch.int16, torch.int32):
+        raise DctqError("symbols must be an int16 or int32 tensor on a HIP device")
+    if not symbols.is_contiguous():
+        raise DctqError("symbols must be contiguous")
+    sb = 2 if symbols.dtype == torch.int16 else 4
+    if symbol_bytes is not None and int(symbol_bytes) != sb:
+        raise DctqError(f"symbol_bytes {symbol_bytes} does not match symbols of {symbols.dtype}")
+    _need_byte_offsets(offsets, None, symbols)
+    if capacity is not None and int(capacity) < 0:
+        raise DctqError("capacity must be >= 0")
+    n = offsets.numel() - 1
+    dev = symbols.device
+    L = lib()
+    ws = torch.empty(int(L.dctq_bits_workspace_bytes(n)) // 4 + 1, dtype=torch.int32, device=dev)
+    boff = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    s = _stream_ptr(stream)
+
+    def run(buf, cap):
+        _check(L.dctq_bits_pack(C.c_void_p(symbols.data_ptr()), sb, C.c_void_p(offsets.data_ptr()), n,
+                                C.c_void_p(boff.data_ptr()), C.c_void_p(buf.data_ptr()) if buf is not None else None,
+                                cap, C.c_void_p(ws.data_ptr()), s))
+        if stream is not None:
+            stream.synchronize()
+        return int(boff[n].item()) & 0xFFFFFFFF
+
+    cap = run(None, 0) if capacity is None else int(capacity)  # offsets only: the total
+    out = torch.empty(max(cap, 4), dtype=torch.uint8, device=dev)
+    total = run(out if cap else None, cap)
+    return out[:min(total, cap)], boff
+
+
+def bits_decode(bytes, offsets, out=None, stream=None):
+    """Inverse of bits_pack, counterpart of rle_decode: int16 [N, 64] blocks from the packed
+    stream (dctq_bits_decode).  Any bytes decode."""
+    import torch
+    if not isinstance(bytes, torch.Tensor) or not bytes.is_cuda or bytes.dtype != torch.uint8:
+        raise DctqError("bytes must be a uint8 tensor on a HIP device")
+    if not bytes.is_contiguous():
+        raise DctqError("bytes must be contiguous")
+    _need_byte_offsets(offsets, None, bytes)
+    n = offsets.numel() - 1
+    if out is None:
+        out = torch.empty((n, 64), dtype=torch.int16, device=bytes.device)
+    _need(out, n * 64, torch.int16, "out", bytes.device)
+    _check(lib().dctq_bits_decode(C.c_void_p(bytes.data_ptr()), C.c_void_p(offsets.data_ptr()), n,
+                                  C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
     return out
 
 

@@ -244,16 +244,13 @@ int dctq_decode_planes(const dctq_plan *plan, const int16_t *const *coef, const 
     return DCTQ_OK;
 }
 
-int dctq_decode_symbols_planes(const dctq_plan *plan, const void *symbols, int symbol_bytes, const uint32_t *offsets,
-                               const int32_t *const *var_num, const dctq_plane *dst, int nplanes, void *stream) {
-    DCTQ_LAUNCH(stream, dctq::kEntryDecodeSymbolsPlanes);
-    if (int rc = dctq::check_plan(plan)) return rc;
-    if (!symbols || !offsets || !dst) return fail(DCTQ_EINVAL, "symbols/offsets/dst is NULL");
-    if (symbol_bytes != 2 && symbol_bytes != 4) return fail(DCTQ_EINVAL, "symbol_bytes must be 2 or 4");
-    if (((uintptr_t)symbols) % 4 || ((uintptr_t)offsets) % 4) return fail(DCTQ_EINVAL, "symbols/offsets must be 4-byte aligned");
+// The destination planes of the fused decoders: geometry, var_num and the concatenated block numbering.
+static int symbol_set(const dctq_plan *plan, const int32_t *const *var_num, const dctq_plane *dst, int nplanes,
+                      dctq::SymbolSet *out) {
     if (nplanes < 1 || nplanes > dctq::kMaxPlanes) return fail(DCTQ_EINVAL, "nplanes must be in [1, 4]");
     if (plan->adaptive && !var_num) return fail(DCTQ_EINVAL, "adaptive decode needs var_num");
-    dctq::SymbolSet ss = {};
+    dctq::SymbolSet &ss = *out;
+    ss = {};
     ss.n = nplanes;
     for (int k = 0; k < nplanes; ++k) {
         if (int rc = dctq::plane_args(&dst[k], &ss.pl[k])) return rc;
@@ -263,9 +260,35 @@ int dctq_decode_symbols_planes(const dctq_plan *plan, const void *symbols, int s
     if (int rc = number_blocks(ss.pl, nplanes, ss.blk_first, 1ll << 26, "more than 2^26 - 1 blocks in one decode"))
         return rc;
     for (int k = nplanes + 1; k <= dctq::kMaxPlanes; ++k) ss.blk_first[k] = ss.blk_first[nplanes];
+    return DCTQ_OK;
+}
+
+int dctq_decode_symbols_planes(const dctq_plan *plan, const void *symbols, int symbol_bytes, const uint32_t *offsets,
+                               const int32_t *const *var_num, const dctq_plane *dst, int nplanes, void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryDecodeSymbolsPlanes);
+    if (int rc = dctq::check_plan(plan)) return rc;
+    if (!symbols || !offsets || !dst) return fail(DCTQ_EINVAL, "symbols/offsets/dst is NULL");
+    if (symbol_bytes != 2 && symbol_bytes != 4) return fail(DCTQ_EINVAL, "symbol_bytes must be 2 or 4");
+    if (((uintptr_t)symbols) % 4 || ((uintptr_t)offsets) % 4) return fail(DCTQ_EINVAL, "symbols/offsets must be 4-byte aligned");
+    dctq::SymbolSet ss;
+    if (int rc = symbol_set(plan, var_num, dst, nplanes, &ss)) return rc;
     HIPCHK(dctq::launch_decode_symbols(ss, symbols, symbol_bytes, offsets, plan->dev, plan->adaptive,
                                        plan->inv_f32 != 0, (hipStream_t)stream, plan->num_cus),
            "decode_symbols launch");
+    return DCTQ_OK;
+}
+
+int dctq_decode_bits_planes(const dctq_plan *plan, const uint8_t *bytes, const uint32_t *offsets,
+                            const int32_t *const *var_num, const dctq_plane *dst, int nplanes, void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryDecodeBitsPlanes);
+    if (int rc = dctq::check_plan(plan)) return rc;
+    if (!bytes || !offsets || !dst) return fail(DCTQ_EINVAL, "bytes/offsets/dst is NULL");
+    if (((uintptr_t)offsets) % 4) return fail(DCTQ_EINVAL, "offsets must be 4-byte aligned");
+    dctq::SymbolSet ss;
+    if (int rc = symbol_set(plan, var_num, dst, nplanes, &ss)) return rc;
+    HIPCHK(dctq::launch_decode_bits(ss, bytes, offsets, plan->dev, plan->adaptive, plan->inv_f32 != 0,
+                                    (hipStream_t)stream, plan->num_cus),
+           "decode_bits launch");
     return DCTQ_OK;
 }
 
@@ -332,6 +355,36 @@ int dctq_rle_decode16(const uint16_t *symbols, const uint32_t *offsets, long lon
     if (((uintptr_t)symbols) % 4) return fail(DCTQ_EINVAL, "symbols must be 4-byte aligned");
     HIPCHK(dctq::launch_rle_decode(symbols, 2, offsets, nblocks, coef, (hipStream_t)stream, device_cus()),
            "rle_decode16 launch");
+    return DCTQ_OK;
+}
+
+size_t dctq_bits_workspace_bytes(long long nblocks) { return dctq::rle_workspace_bytes(nblocks < 1 ? 1 : nblocks); }
+
+int dctq_bits_pack(const void *symbols, int symbol_bytes, const uint32_t *sym_offsets, long long nblocks,
+                   uint32_t *offsets, uint8_t *bytes, long long bytes_capacity, void *workspace, void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryBitsPack);
+    if (int rc = rle_args(symbols, sym_offsets, nblocks)) return rc;
+    if (!offsets || !workspace) return fail(DCTQ_EINVAL, "offsets/workspace is NULL");
+    if (symbol_bytes != 2 && symbol_bytes != 4) return fail(DCTQ_EINVAL, "symbol_bytes must be 2 or 4");
+    // offsets are 32-bit and a block takes up to 368 B
+    if (368 * nblocks >= (1ll << 32)) return fail(DCTQ_EINVAL, "368 * nblocks must stay below 2^32");
+    if (bytes_capacity < 0) return fail(DCTQ_EINVAL, "bytes_capacity < 0");
+    if (((uintptr_t)symbols) % 4 || ((uintptr_t)sym_offsets) % 4 || ((uintptr_t)offsets) % 4 || ((uintptr_t)bytes) % 4)
+        return fail(DCTQ_EINVAL, "symbols/sym_offsets/offsets/bytes must be 4-byte aligned");
+    HIPCHK(dctq::launch_bits_pack(symbols, symbol_bytes, sym_offsets, nblocks, offsets, bytes,
+                                  bytes ? (unsigned long long)bytes_capacity : 0ull, workspace, (hipStream_t)stream,
+                                  device_cus()),
+           "bits_pack launch");
+    return DCTQ_OK;
+}
+
+int dctq_bits_decode(const uint8_t *bytes, const uint32_t *offsets, long long nblocks, int16_t *coef, void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryBitsDecode);
+    if (int rc = rle_args(bytes, offsets, nblocks)) return rc;
+    if (!coef) return fail(DCTQ_EINVAL, "coef is NULL");
+    if (((uintptr_t)offsets) % 4 || ((uintptr_t)coef) % 16) return fail(DCTQ_EINVAL, "offsets must be 4-byte, coef 16-byte aligned");
+    HIPCHK(dctq::launch_bits_decode(bytes, offsets, nblocks, coef, (hipStream_t)stream, device_cus()),
+           "bits_decode launch");
     return DCTQ_OK;
 }
 

@@ -55,6 +55,9 @@ enum Entry : int {
     kEntryHuffmanBits,
     kEntryHuffmanBitsPlanes,
     kEntryDistortionPlanes,
+    kEntryBitsPack,
+    kEntryBitsDecode,
+    kEntryDecodeBitsPlanes,
     kEntrySynchronize,
 };
 static_assert(kEntrySynchronize < 32, "LaunchIsolation keeps one bit per entry point in a uint32_t");
@@ -310,6 +313,16 @@ hipError_t launch_distortion(const EncodeSet &es, const DevTables *dev, int adap
                              hipStream_t stream, int num_cus);
 hipError_t launch_rle_decode(const void *symbols, int symbol_bytes, const uint32_t *offsets, long long nblk,
                              int16_t *coef, hipStream_t stream, int num_cus);
+// run-length symbols -> the bit-packed stream "bits v1" (bits.hip): byte offsets (complete), then the
+// bytes below `capacity`; ws: rle_workspace_bytes(nblk)
+hipError_t launch_bits_pack(const void *symbols, int symbol_bytes, const uint32_t *sym_offsets, long long nblk,
+                            uint32_t *offsets, uint8_t *bytes, unsigned long long capacity, void *ws,
+                            hipStream_t stream, int num_cus);
+// ... back to coefficients (bits.hip), and straight to u8 pixels in the planes of ss (decode_bits.hip)
+hipError_t launch_bits_decode(const uint8_t *bytes, const uint32_t *offsets, long long nblk, int16_t *coef,
+                              hipStream_t stream, int num_cus);
+hipError_t launch_decode_bits(const SymbolSet &ss, const uint8_t *bytes, const uint32_t *offsets, const DevTables *dev,
+                              int adaptive, bool inv_f32, hipStream_t stream, int num_cus);
 // diagnostic library (fdct8_diag.hip): the lane-per-block fp64 kernels (variant 1)
 hipError_t launch_fdct8_float(const PlaneArgs &p, const DevTables *dev, float *coef, hipStream_t stream);
 hipError_t launch_idct8(const DevTables *dev, int adaptive, const int16_t *coef, const int32_t *var_num,

@@ -248,6 +248,70 @@ int dctq_rle_decode16(const uint16_t *symbols, const uint32_t *offsets, long lon
 int dctq_rle_decode(const uint32_t *symbols, const uint32_t *offsets, long long nblocks, int16_t *coef,
                     void *stream);
 
+/* Bit-packed coefficient streams, format "bits v1": a fixed, table-free
+ * variable-length code for the run-length symbols above (the reference stops at a
+ * size estimate and has no bitstream writer; tools/bits_ref.py states the format
+ * in plain Python).
+ *   Layout.   Block b of the concatenated block numbering owns bytes
+ *             [offsets[b], offsets[b+1]) of one byte buffer; offsets has N + 1
+ *             uint32_t entries, offsets[N] the total.  Blocks follow each other
+ *             with no gap; each starts on a byte boundary, its last byte padded
+ *             with zero bits.
+ *   Bits.     Bit i of a block is bit 7 - (i % 8) of its byte i / 8 (MSB first).
+ *   ue(k), k >= 0.  x = k + 1 of bit length n: n - 1 zero bits, then x in n bits
+ *             (2n - 1 bits: Exp-Golomb of order 0).
+ *   Symbol (value v, run r).  ue(min(r, 64)), then ue(m), m = 2v - 1 for v > 0,
+ *             else -2v (v = -32768: m = 65536, 33 bits).
+ *   Block.    Its symbols in order, at most the first 64 (neither that nor the run
+ *             clamp changes what dctq_rle_decode makes of the block); at most
+ *             64 * 46 bits = 368 B, below 272 B for a stream of this encoder.
+ *   Decoding a block.  pos = 0; read ue -> r, ue -> m;
+ *             v = (int16_t)(m & 1 ? (m + 1) >> 1 : -(m >> 1)); pos += r; store v at
+ *             zigzag position pos if pos < 64; pos += 1.  Stop when pos >= 64, or
+ *             after 64 symbols, or at a bad code: a zero prefix of more than 16
+ *             bits, or a code that would use a bit past the block's last byte.  A
+ *             bad code ends the block and its symbol is dropped; positions never
+ *             written are 0; an empty block decodes to zeros.  ANY bytes are
+ *             therefore a valid input (with non-decreasing offsets), and nothing
+ *             outside [offsets[b0], offsets[b0 + nb]) of a 64-block tile is read.
+ *
+ * dctq_bits_pack: the packed stream of a symbol stream (symbol_bytes 4: uint32_t
+ * (uint16_t)value | run << 16, any values and runs; 2: uint16_t (run & 63) << 10 |
+ * (value & 0x3FF), 0x0000 = (0, 64): the outputs of dctq_encode_planes /
+ * dctq_encode_planes16, or anybody's), sym_offsets[b] the first symbol of block b
+ * (nblocks + 1 entries).  offsets (nblocks + 1 entries, not sym_offsets) is always
+ * complete; bytes at index >= bytes_capacity are not written, and bytes == NULL or
+ * bytes_capacity 0 computes the offsets only -- as dctq_encode_planes treats its
+ * symbols.  For ANY symbol input
+ *   dctq_bits_decode(dctq_bits_pack(S)) == dctq_rle_decode(S).
+ * symbols, sym_offsets, offsets and bytes 4-byte aligned; workspace: device memory
+ * of dctq_bits_workspace_bytes(nblocks) bytes; 1 <= nblocks < 2^26 and
+ * 368 * nblocks < 2^32 (offsets are 32-bit: nblocks <= 11 671 106), else
+ * DCTQ_EINVAL.  Four launches on stream (count, scan, fix-up, emit); allocates
+ * nothing. */
+size_t dctq_bits_workspace_bytes(long long nblocks);
+int dctq_bits_pack(const void *symbols, int symbol_bytes, const uint32_t *sym_offsets, long long nblocks,
+                   uint32_t *offsets, uint8_t *bytes, long long bytes_capacity, void *workspace, void *stream);
+/* The inverse, and the counterpart of dctq_rle_decode: coef[b][64] (natural
+ * order) from bytes[offsets[b] .. offsets[b+1]).  bytes of any alignment, offsets
+ * 4-byte and coef 16-byte aligned; 1 <= nblocks < 2^26. */
+int dctq_bits_decode(const uint8_t *bytes, const uint32_t *offsets, long long nblocks, int16_t *coef, void *stream);
+/* Decoder from the packed stream: "bits v1" bytes -> u8 pixels in ONE launch,
+ * with no coefficient buffer.  The contract is an equivalence: the pixels are,
+ * bit for bit, what these two calls produce --
+ *   1. dctq_bits_decode of the N blocks into one buffer c;
+ *   2. dctq_decode_planes(plan, {c + 64 * first_k}, var_num, dst, nplanes), where
+ *      first_k is the number of blocks in the planes before plane k
+ * -- for any bytes, with the error bound of dctq_decode_planes for the domain
+ * the decoded coefficients fall in (a packed symbol carries any int16).
+ * Block numbering, var_num (required for adaptive plans, ignored otherwise),
+ * dst, the bytes outside width x height that are not touched and N < 2^26 are as
+ * for dctq_decode_symbols_planes.  P + 4 B read (P: the block's packed bytes) +
+ * 64 B written per block (+ 4 B adaptive).  Asynchronous on stream; allocates
+ * nothing. */
+int dctq_decode_bits_planes(const dctq_plan *plan, const uint8_t *bytes, const uint32_t *offsets,
+                            const int32_t *const *var_num, const dctq_plane *dst, int nplanes, void *stream);
+
 /* Per-block Huffman size: bits[b] = what the reference's pipeline
  * reports for block b coded on its own (tests/test_entropy.c:329-341):
  * run_length_encode -> build_huffman_codes -> get_encoded_size
