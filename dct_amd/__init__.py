@@ -30,6 +30,12 @@ class _Plane(C.Structure):
                 ("width", C.c_int), ("height", C.c_int), ("nframes", C.c_int)]
 
 
+class _Rgb(C.Structure):
+    _fields_ = [("pixels", C.c_void_p), ("stride", C.c_longlong), ("frame_stride", C.c_longlong),
+                ("channel_stride", C.c_longlong), ("pixel_step", C.c_int),
+                ("width", C.c_int), ("height", C.c_int), ("nframes", C.c_int)]
+
+
 _lib = None
 _diag = None
 DIAG_PATH = os.path.join(HERE, "libdct_amd_diag.so")
@@ -68,6 +74,8 @@ def _bind(L: C.CDLL, diagnostic: bool) -> C.CDLL:
         "dctq_huffman_bits": ([vp, ll, vp, vp], i),
         "dctq_huffman_bits_planes": ([vp, C.POINTER(_Plane), i, vp, vp], i),
         "dctq_distortion_planes": ([vp, C.POINTER(_Plane), i, vp, vp], i),
+        "dctq_rgb_to_ycbcr_planes": ([C.POINTER(_Rgb), C.POINTER(_Plane), C.POINTER(_Plane), C.POINTER(_Plane), vp], i),
+        "dctq_ycbcr_to_rgb_planes": ([C.POINTER(_Plane), C.POINTER(_Plane), C.POINTER(_Plane), C.POINTER(_Rgb), vp], i),
         "dctq_stream_release": ([vp], i),
     }
     if diagnostic:
@@ -686,6 +694,103 @@ def bits_decode(bytes, offsets, out=None, stream=None):
     _need(out, n * 64, torch.int16, "out", bytes.device)
     _check(lib().dctq_bits_decode(C.c_void_p(bytes.data_ptr()), C.c_void_p(offsets.data_ptr()), n,
                                   C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+    return out
+
+
+def rgb_desc(t, bgr: bool = False):
+    """Describe a uint8 device tensor [F, H, W, C] or [H, W, C] (channel axis last in the shape,
+    C 3 or 4) as an RGB picture stack, without a copy.  Unit channel stride and a pixel stride of
+    3 or 4 is interleaved RGB / RGBX (a contiguous HWC tensor); unit pixel stride is planar (e.g.
+    chw.permute(0, 2, 3, 1) of a contiguous [F, 3, H, W] tensor: channel stride H * W); rows and
+    frames may be padded.  bgr=True describes the same memory with R and B exchanged (BGR / BGRX,
+    or the channel planes in reverse).  Strides the descriptor cannot express raise DctqError;
+    alignment is the library's to check (include/dct_amd.h)."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        raise DctqError("rgb must be a uint8 tensor")
+    if t.dim() == 3:
+        t = t.unsqueeze(0)
+    if t.dim() != 4 or t.shape[3] not in (3, 4):
+        raise DctqError("rgb must be [H, W, C] or [F, H, W, C] with C 3 or 4 (channel axis last)")
+    if not t.is_cuda:
+        raise DctqError("rgb must be a tensor on a HIP device")
+    f, h, w, c = t.shape
+    sf, sh, sw, sc = t.stride()
+    if sw == 1 and sc != 1:
+        step, cs = 1, sc
+    elif sc == 1 and sw in (3, 4) and c <= sw:
+        step, cs = sw, 1
+    else:
+        raise DctqError(f"rgb strides {tuple(t.stride())} are neither interleaved (channel stride 1, pixel stride "
+                        "3 or 4) nor planar (pixel stride 1)")
+    if sh < w * step or (f > 1 and sf < sh * h):
+        raise DctqError(f"rgb strides {tuple(t.stride())}: rows or frames overlap")
+    ptr = t.data_ptr() + (2 * cs if bgr else 0)
+    return _Rgb(ptr, sh, sf if f > 1 else sh * h, -cs if bgr else cs, step, w, h, f)
+
+
+def _same_device(ts, what):
+    import torch
+    if any(not isinstance(t, torch.Tensor) for t in ts):
+        raise DctqError(f"{what} must be tensors")
+    if any(t.device != ts[0].device for t in ts):
+        raise DctqError(f"{what} must be on one device")
+
+
+def rgb_to_ycbcr(rgb, subsampling: str = "420", outs=None, bgr: bool = False, stream=None):
+    """An RGB picture stack (rgb_desc(rgb, bgr)) -> (y, cb, cr) u8 planes in ONE launch
+    (dctq_rgb_to_ycbcr_planes): y [F, H, W] and cb, cr [F, H/2, W/2] ("420") or [F, H, W]
+    ("444"), ready for Plan.forward_quant_planes([y, cb, cr]) and Plan.encode_bits_planes.
+    Exact integer BT.601 full range as tools/color_ref.py states it.  outs, if given, are the
+    three u8 tensors and may be strided views (bytes outside width x height are not touched)."""
+    import torch
+    d = rgb_desc(rgb, bgr)
+    if subsampling not in ("420", "444"):
+        raise DctqError('subsampling must be "420" or "444"')
+    sub = 2 if subsampling == "420" else 1
+    if d.width % (8 * sub) or d.height % (8 * sub):
+        raise DctqError(f"{subsampling}: width and height must be multiples of {8 * sub}, got {d.width} x {d.height}")
+    shapes = [(d.nframes, d.height, d.width)] + [(d.nframes, d.height // sub, d.width // sub)] * 2
+    if outs is None:
+        outs = [torch.empty(s_, dtype=torch.uint8, device=rgb.device) for s_ in shapes]
+    if len(outs) != 3:
+        raise DctqError(f"outs needs three planes (y, cb, cr), got {len(outs)}")
+    _same_device([rgb, *outs], "rgb and outs")
+    descs = [plane_desc(o) for o in outs]
+    for name, p, want in zip(("y", "cb", "cr"), descs, shapes):
+        if (p.nframes, p.height, p.width) != want:
+            raise DctqError(f"outs: {name} is {(p.nframes, p.height, p.width)}, {subsampling} of rgb needs {want}")
+    _check(lib().dctq_rgb_to_ycbcr_planes(C.byref(d), C.byref(descs[0]), C.byref(descs[1]), C.byref(descs[2]),
+                                          _stream_ptr(stream)))
+    return tuple(outs)
+
+
+def ycbcr_to_rgb(y, cb, cr, out=None, channels: int = 3, planar: bool = False, bgr: bool = False, stream=None):
+    """(y, cb, cr) u8 planes (4:2:0 or 4:4:4, read from their shapes) -> an RGB picture stack in
+    ONE launch (dctq_ycbcr_to_rgb_planes), the exact integer inverse of tools/color_ref.py.
+    out None: allocates u8 [F, H, W, channels] (channels 3 or 4; the fourth byte is 255), or with
+    planar=True [F, 3, H, W], returned as its [F, H, W, 3] view.  Otherwise writes into out as
+    rgb_desc(out, bgr) describes it (strided views are fine: padding is not touched).  bgr=True
+    stores B where R would go and R where B would."""
+    import torch
+    _same_device([y, cb, cr], "y, cb and cr")
+    descs = [plane_desc(p) for p in (y, cb, cr)]
+    f, h, w = descs[0].nframes, descs[0].height, descs[0].width
+    if any(p.nframes != f for p in descs):
+        raise DctqError("y, cb and cr differ in the number of frames")
+    if out is None:
+        if planar:
+            out = torch.empty((f, 3, h, w), dtype=torch.uint8, device=y.device).permute(0, 2, 3, 1)
+        elif channels in (3, 4):
+            out = torch.empty((f, h, w, channels), dtype=torch.uint8, device=y.device)
+        else:
+            raise DctqError("channels must be 3 or 4")
+    d = rgb_desc(out, bgr)
+    _same_device([y, out], "the planes and out")
+    if (d.nframes, d.height, d.width) != (f, h, w):
+        raise DctqError(f"out is {(d.nframes, d.height, d.width)} (F, H, W), y is {(f, h, w)}")
+    _check(lib().dctq_ycbcr_to_rgb_planes(C.byref(descs[0]), C.byref(descs[1]), C.byref(descs[2]), C.byref(d),
+                                          _stream_ptr(stream)))
     return out
 
 

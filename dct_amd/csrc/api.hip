@@ -429,6 +429,82 @@ int dctq_distortion_planes(const dctq_plan *plan, const dctq_plane *planes, int 
     return DCTQ_OK;
 }
 
+// The colour kernels' arguments from an RGB stack and its three planes, everything checked:
+// *pixel_step and *s420 select the kernel.
+static int color_args(const dctq_rgb *rgb, const dctq_plane *y, const dctq_plane *cb, const dctq_plane *cr,
+                      dctq::ColorArgs *out, int *pixel_step, bool *s420) {
+    if (!rgb || !rgb->pixels) return fail(DCTQ_EINVAL, "rgb/pixels is NULL");
+    const int step = rgb->pixel_step;
+    if (step != 1 && step != 3 && step != 4) return fail(DCTQ_EINVAL, "pixel_step must be 1, 3 or 4");
+    const long long cs = rgb->channel_stride;
+    if (step == 1 ? (cs == 0 || cs % 4) : (cs != 1 && cs != -1))
+        return fail(DCTQ_EINVAL, "channel_stride must be +1 or -1 (interleaved) or a non-zero multiple of 4 (planar)");
+    // the lowest byte of pixel (0,0): its B byte when the order is B, G, R
+    uint8_t *first = (uint8_t *)rgb->pixels - (step != 1 && cs == -1 ? 2 : 0);
+    if (((uintptr_t)first) % 4 || rgb->stride % 4 || rgb->frame_stride % 4)
+        return fail(DCTQ_EINVAL, "rgb: the lowest byte of pixel (0,0) must be 4-byte aligned, stride and frame_stride "
+                                 "multiples of 4");
+    dctq::PlaneArgs py, pb, pr;
+    if (int rc = dctq::plane_args(y, &py)) return rc;
+    if (int rc = dctq::plane_args(cb, &pb)) return rc;
+    if (int rc = dctq::plane_args(cr, &pr)) return rc;
+    if (rgb->width != y->width || rgb->height != y->height)
+        return fail(DCTQ_EINVAL, "the RGB stack and the Y plane differ in width or height");
+    if (rgb->nframes != y->nframes || cb->nframes != y->nframes || cr->nframes != y->nframes)
+        return fail(DCTQ_EINVAL, "the RGB stack and the planes differ in nframes");
+    if (rgb->stride < (long long)rgb->width * step) return fail(DCTQ_EINVAL, "rgb: stride smaller than one row");
+    if (rgb->nframes > 1 && rgb->frame_stride < rgb->stride * (long long)rgb->height)
+        return fail(DCTQ_EINVAL, "rgb: frame_stride smaller than one frame");
+    if (step == 1 && (cs < 0 ? -cs : cs) < rgb->width) return fail(DCTQ_EINVAL, "rgb: channel_stride smaller than one row");
+    if (cb->width != cr->width || cb->height != cr->height) return fail(DCTQ_EINVAL, "Cb and Cr differ in size");
+    const bool full = cb->width == y->width && cb->height == y->height;
+    const bool half = 2ll * cb->width == y->width && 2ll * cb->height == y->height;
+    if (!full && !half)
+        return fail(DCTQ_EINVAL, "chroma must be luma's size (4:4:4) or exactly half of it in both directions (4:2:0)");
+    const long long per_row = y->width / 8, per_frame = per_row * (y->height / (half ? 2 : 1));
+    if (per_frame * y->nframes >= (1ll << 31)) return fail(DCTQ_EINVAL, "2^31 patches or more in one call");
+    dctq::ColorArgs &a = *out;
+    a = {};
+    a.rgb = first;
+    a.rgb_stride = rgb->stride;
+    a.rgb_frame_stride = rgb->frame_stride;
+    a.channel_stride = cs;
+    a.swap = step != 1 && cs == -1;
+    a.y = const_cast<uint8_t *>(y->pixels), a.y_stride = y->stride, a.y_frame_stride = y->frame_stride;
+    a.cb = const_cast<uint8_t *>(cb->pixels), a.cb_stride = cb->stride, a.cb_frame_stride = cb->frame_stride;
+    a.cr = const_cast<uint8_t *>(cr->pixels), a.cr_stride = cr->stride, a.cr_frame_stride = cr->frame_stride;
+    a.npatch = (uint32_t)(per_frame * y->nframes);
+    a.per_row = (uint32_t)per_row;
+    a.per_frame = (uint32_t)per_frame;
+    a.div_row = dctq::make_fastdiv(a.per_row);
+    a.div_frame = dctq::make_fastdiv(a.per_frame);
+    *pixel_step = step;
+    *s420 = half;
+    return DCTQ_OK;
+}
+
+int dctq_rgb_to_ycbcr_planes(const dctq_rgb *src, const dctq_plane *y, const dctq_plane *cb, const dctq_plane *cr,
+                             void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryRgbToYcbcrPlanes);
+    dctq::ColorArgs a;
+    int step;
+    bool s420;
+    if (int rc = color_args(src, y, cb, cr, &a, &step, &s420)) return rc;
+    HIPCHK(dctq::launch_rgb_to_ycc(a, step, s420, (hipStream_t)stream, device_cus()), "rgb_to_ycc launch");
+    return DCTQ_OK;
+}
+
+int dctq_ycbcr_to_rgb_planes(const dctq_plane *y, const dctq_plane *cb, const dctq_plane *cr, const dctq_rgb *dst,
+                             void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryYcbcrToRgbPlanes);
+    dctq::ColorArgs a;
+    int step;
+    bool s420;
+    if (int rc = color_args(dst, y, cb, cr, &a, &step, &s420)) return rc;
+    HIPCHK(dctq::launch_ycc_to_rgb(a, step, s420, (hipStream_t)stream, device_cus()), "ycc_to_rgb launch");
+    return DCTQ_OK;
+}
+
 int dctq_device_count(int *count) {
     DCTQ_ENTRY;
     HIPCHK(hipGetDeviceCount(count), "hipGetDeviceCount");

@@ -58,6 +58,8 @@ enum Entry : int {
     kEntryBitsPack,
     kEntryBitsDecode,
     kEntryDecodeBitsPlanes,
+    kEntryRgbToYcbcrPlanes,
+    kEntryYcbcrToRgbPlanes,
     kEntrySynchronize,
 };
 static_assert(kEntrySynchronize < 32, "LaunchIsolation keeps one bit per entry point in a uint32_t");
@@ -230,6 +232,20 @@ struct SymbolSet {
     int n;
 };
 
+// The colour kernels' arguments (color.hip): an RGB picture stack and its Y, Cb, Cr planes.
+// A patch is 8 pixels by 2 rows (4:2:0) or 1 row (4:4:4); patches are numbered in raster
+// order over the frames, npatch < 2^31.
+struct ColorArgs {
+    uint8_t *rgb;               // interleaved: the lowest byte of pixel (0,0) of frame 0; planar: its R byte
+    long long rgb_stride, rgb_frame_stride;
+    long long channel_stride;   // planar: bytes from the R plane to G's and from G's to B's
+    int swap;                   // interleaved: the pixel's bytes are B, G, R in memory
+    uint8_t *y, *cb, *cr;       // read by the inverse, written by the forward
+    long long y_stride, y_frame_stride, cb_stride, cb_frame_stride, cr_stride, cr_frame_stride;
+    uint32_t npatch, per_row, per_frame;
+    FastDiv div_row, div_frame;  // by per_row and by per_frame
+};
+
 // Plane selection over a PlaneSet or a DecodeSet (64- or 32-block batches).
 // Coefficient / var_num pointer of plane k (wave-uniform or not: a select chain, no
 // indexed kernel-argument loads).
@@ -323,6 +339,9 @@ hipError_t launch_bits_decode(const uint8_t *bytes, const uint32_t *offsets, lon
                               hipStream_t stream, int num_cus);
 hipError_t launch_decode_bits(const SymbolSet &ss, const uint8_t *bytes, const uint32_t *offsets, const DevTables *dev,
                               int adaptive, bool inv_f32, hipStream_t stream, int num_cus);
+// RGB <-> Y/Cb/Cr planes (color.hip); pixel_step 1, 3 or 4
+hipError_t launch_rgb_to_ycc(const ColorArgs &a, int pixel_step, bool s420, hipStream_t stream, int num_cus);
+hipError_t launch_ycc_to_rgb(const ColorArgs &a, int pixel_step, bool s420, hipStream_t stream, int num_cus);
 // diagnostic library (fdct8_diag.hip): the lane-per-block fp64 kernels (variant 1)
 hipError_t launch_fdct8_float(const PlaneArgs &p, const DevTables *dev, float *coef, hipStream_t stream);
 hipError_t launch_idct8(const DevTables *dev, int adaptive, const int16_t *coef, const int32_t *var_num,

@@ -356,6 +356,54 @@ int dctq_huffman_bits_planes(const dctq_plan *plan, const dctq_plane *planes, in
 int dctq_distortion_planes(const dctq_plan *plan, const dctq_plane *planes, int nplanes, uint32_t *sse,
                            void *stream);
 
+/* Colour front and back end: an RGB picture stack to the Y, Cb, Cr planes the entry
+ * points above take, and decoded planes back to a picture.  The reference has no
+ * colour code; the definition is this library's own, exact and integer, and
+ * tools/color_ref.py states it in plain Python.  Full-range BT.601 (JFIF) in 16-bit
+ * fixed point on int32, >> an arithmetic shift:
+ *   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *   Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16
+ *   Cr = ( 32768 R - 27439 G -  5329 B + 8388608 + 32767) >> 16
+ * (all three lie in [0, 255] for every colour: no clamp), and back, with
+ * cb = Cb - 128, cr = Cr - 128 and clamp to [0, 255]:
+ *   R = clamp(Y + (( 91881 cr + 32768) >> 16))
+ *   G = clamp(Y + ((-22554 cb - 46802 cr + 32768) >> 16))
+ *   B = clamp(Y + ((116130 cb + 32768) >> 16))
+ * Subsampling is read from the geometry: chroma planes of luma's width and height
+ * are 4:4:4; of exactly half in both, 4:2:0, where chroma sample (i, j) =
+ * (c00 + c01 + c10 + c11 + 2) >> 2 over the u8 Cb (Cr) of pixels (2i..2i+1,
+ * 2j..2j+1), and on the way back serves those four pixels; anything else is
+ * DCTQ_EINVAL.  In 4:4:4 the round trip is within 1 of the source in every channel.
+ *
+ * A packed or planar RGB picture stack in device memory.  RGB: pixel_step 3,
+ * channel_stride +1; RGBX: 4, +1; BGR / BGRX: the same with channel_stride -1 and
+ * pixels at the R byte (the third of the pixel); planar: pixel_step 1 and
+ * channel_stride the distance between the channel planes, either sign. */
+typedef struct {
+    void *pixels;              /* the R byte of pixel (0,0) of frame 0 */
+    long long stride;          /* bytes between rows */
+    long long frame_stride;    /* bytes between frames */
+    long long channel_stride;  /* bytes from R to G and from G to B: +1 (RGB/RGBX), -1 (BGR/BGRX),
+                                  or a plane size, either sign (planar) */
+    int pixel_step;            /* bytes between pixels of one channel: 1 (planar), 3 or 4 (interleaved) */
+    int width, height, nframes;
+} dctq_rgb;
+/* No plan: the transform does not depend on quality.  y, cb, cr as every dctq_plane
+ * (so 4:2:0 needs luma multiples of 16); all three and the RGB stack agree on
+ * nframes, y and the RGB stack on width and height.  RGB alignment: the lowest byte
+ * address of pixel (0,0) -- pixels, or pixels - 2 when channel_stride is -1 -- is
+ * 4-byte aligned, stride and frame_stride are multiples of 4 (and, planar,
+ * channel_stride too); stride covers a row, frame_stride a frame.  The fourth byte
+ * of a 4-byte pixel is ignored on input and written as 255 on output.  Bytes outside
+ * width x height of any destination -- row padding, the gaps between frames and
+ * channels -- are not touched.  3 B read and 1.5 B written per pixel in 4:2:0 (4 and
+ * 1.5 for 4-byte pixels; 3 and 3 in 4:4:4), the reverse for dctq_ycbcr_to_rgb_planes;
+ * one launch each, asynchronous on stream; allocates nothing. */
+int dctq_rgb_to_ycbcr_planes(const dctq_rgb *src, const dctq_plane *y, const dctq_plane *cb,
+                             const dctq_plane *cr, void *stream);
+int dctq_ycbcr_to_rgb_planes(const dctq_plane *y, const dctq_plane *cb, const dctq_plane *cr,
+                             const dctq_rgb *dst, void *stream);
+
 /* The calling thread forgets `stream` (call it before hipStreamDestroy): the
  * library keeps no per-stream device memory, only each thread's list of the
  * streams it has launched on, and a stream later created at the same handle
