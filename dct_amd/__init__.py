@@ -70,6 +70,9 @@ def _bind(L: C.CDLL, diagnostic: bool) -> C.CDLL:
         "dctq_bits_pack": ([vp, i, vp, ll, vp, vp, ll, vp, vp], i),
         "dctq_bits_decode": ([vp, vp, ll, vp, vp], i),
         "dctq_decode_bits_planes": ([vp, vp, vp, vp, C.POINTER(_Plane), i, vp], i),
+        "dctq_block_lengths": ([vp, ll, i, vp, vp, vp], i),
+        "dctq_block_offsets_workspace_bytes": ([ll], C.c_size_t),
+        "dctq_block_offsets": ([vp, i, ll, vp, vp, vp], i),
         "dctq_plan_symbol_bytes": ([vp], i),
         "dctq_huffman_bits": ([vp, ll, vp, vp], i),
         "dctq_huffman_bits_planes": ([vp, C.POINTER(_Plane), i, vp, vp], i),
@@ -792,6 +795,288 @@ def ycbcr_to_rgb(y, cb, cr, out=None, channels: int = 3, planar: bool = False, b
     _check(lib().dctq_ycbcr_to_rgb_planes(C.byref(descs[0]), C.byref(descs[1]), C.byref(descs[2]), C.byref(d),
                                           _stream_ptr(stream)))
     return out
+
+
+# ---- the container "frame v1" (include/dct_amd.h, tools/frame_ref.py) -------------------------------
+FRAME_MAGIC = b"DCTQFRM1"
+_FRAME_MAX_BLOCKS = 11_671_106   # 368 * nblocks < 2^32, as dctq_bits_pack
+_FRAME_HEAD = 48 + 16 * 4        # the longest header
+
+
+def _align16(n: int) -> int:
+    return (n + 15) // 16 * 16
+
+
+def _on_stream(stream):
+    """torch's own copies and fills go to `stream` too (None: the current one)."""
+    import contextlib
+    import torch
+    return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+
+
+def _read_back(t, stream):
+    """A small device tensor as a list of ints (one sync, of `stream` when given)."""
+    with _on_stream(stream):
+        return t.cpu().tolist()
+
+
+def block_lengths(offsets, length_bytes=None, stream=None):
+    """Byte offsets int32 [N+1] (uint32 bit patterns, as bits_pack returns them) -> (lengths,
+    length_bytes): lengths[b] = offsets[b+1] - offsets[b] as uint8 [N] (length_bytes 1) or int16
+    [N] holding uint16 bit patterns (2) (dctq_block_lengths).  length_bytes None tries 1, reads
+    the largest length back (one sync) and reruns with 2 only when a block exceeds 255 B.  A
+    length that does not fit length_bytes (above 65535 for None: no offsets of a packed stream)
+    raises DctqError."""
+    import torch
+    _need_byte_offsets(offsets, None, offsets)
+    if length_bytes is not None and int(length_bytes) not in (1, 2):
+        raise DctqError("length_bytes must be 1, 2 or None")
+    n = offsets.numel() - 1
+    mx = torch.empty(1, dtype=torch.int32, device=offsets.device)
+    for lb in ((1, 2) if length_bytes is None else (int(length_bytes),)):
+        out = torch.empty(n, dtype=torch.uint8 if lb == 1 else torch.int16, device=offsets.device)
+        _check(lib().dctq_block_lengths(C.c_void_p(offsets.data_ptr()), n, lb, C.c_void_p(out.data_ptr()),
+                                        C.c_void_p(mx.data_ptr()), _stream_ptr(stream)))
+        longest = _read_back(mx, stream)[0] & 0xFFFFFFFF
+        if longest < 1 << (8 * lb):
+            return out, lb
+    raise DctqError(f"a block of {longest} bytes does not fit length_bytes {lb}")
+
+
+def block_offsets(lengths, out=None, stream=None):
+    """The inverse of block_lengths (dctq_block_offsets): int32 [N+1] exclusive prefix sums of
+    min(length, 368), the last entry the total.  lengths.dtype picks the width: uint8 is 1,
+    int16 or uint16 is 2."""
+    import torch
+    two = {torch.int16} | ({torch.uint16} if hasattr(torch, "uint16") else set())
+    if not isinstance(lengths, torch.Tensor) or not lengths.is_cuda or lengths.dtype not in {torch.uint8} | two:
+        raise DctqError("lengths must be a uint8, int16 or uint16 tensor on a HIP device")
+    if not lengths.is_contiguous() or lengths.numel() < 1:
+        raise DctqError("lengths must be contiguous and hold at least one block")
+    n = lengths.numel()
+    if out is None:
+        out = torch.empty(n + 1, dtype=torch.int32, device=lengths.device)
+    _need(out, n + 1, torch.int32, "out", lengths.device)
+    L = lib()
+    ws = torch.empty(int(L.dctq_block_offsets_workspace_bytes(n)) // 4 + 1, dtype=torch.int32, device=lengths.device)
+    _check(L.dctq_block_offsets(C.c_void_p(lengths.data_ptr()), 1 if lengths.dtype == torch.uint8 else 2, n,
+                                C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), _stream_ptr(stream)))
+    return out
+
+
+def _frame_geometry(shapes, colour) -> int:
+    """The plane records' rules of frame v1 for shapes [(F, H, W)]; returns nblocks."""
+    if not 1 <= len(shapes) <= 4:
+        raise DctqError("frame: nplanes must be 1..4")
+    n = 0
+    for f, h, w in shapes:
+        if w < 8 or h < 8 or w % 8 or h % 8 or f < 1:
+            raise DctqError(f"frame: plane {w} x {h} x {f}: width and height must be multiples of 8, nframes >= 1")
+        n += f * (h // 8) * (w // 8)
+    if not 1 <= n <= _FRAME_MAX_BLOCKS:
+        raise DctqError(f"frame: nblocks {n} outside 1..{_FRAME_MAX_BLOCKS}")
+    if colour:
+        if len(shapes) != 3:
+            raise DctqError("frame: colour needs three planes")
+        (f, h, w), cb, cr = shapes
+        if cb != cr or cb[0] != f or ((cb[1], cb[2]) != (h, w) and (2 * cb[1], 2 * cb[2]) != (h, w)):
+            raise DctqError("frame: colour needs chroma planes of 4:4:4 or 4:2:0 of plane 0")
+    return n
+
+
+def _frame_sections(header_bytes, nblocks, length_bytes, adaptive, payload_bytes):
+    """(starts, total): where the lengths, (var_num) and payload sections start, and the payload's end."""
+    at, starts = header_bytes, []
+    for size in [nblocks * length_bytes] + ([4 * nblocks] if adaptive else []) + [payload_bytes]:
+        at = _align16(at)
+        starts.append(at)
+        at += size
+    return starts, at
+
+
+def _frame_header(head: bytes, buflen: int) -> dict:
+    """The header of a frame v1 container of buflen bytes from its first min(buflen, 112) bytes,
+    with everything that can be refused without the lengths refused (DctqError)."""
+    import struct
+    if buflen < 48 or len(head) < 48:
+        raise DctqError("frame: shorter than the 48-byte fixed header")
+    if head[:8] != FRAME_MAGIC:
+        raise DctqError("frame: bad magic")
+    header_bytes, quality, adaptive, nplanes, length_bytes, colour = struct.unpack_from("<IBBBBB", head, 8)
+    nblocks, payload_bytes, total = struct.unpack_from("<QQQ", head, 24)
+    if not 1 <= quality <= 100 or adaptive > 1 or not 1 <= nplanes <= 4 or length_bytes not in (1, 2) or colour > 1:
+        raise DctqError("frame: a header field is out of range")
+    if any(head[17:24]):
+        raise DctqError("frame: reserved bytes are not 0")
+    if header_bytes != 48 + 16 * nplanes:
+        raise DctqError("frame: header_bytes does not match nplanes")
+    if buflen < header_bytes or len(head) < header_bytes:
+        raise DctqError("frame: shorter than header_bytes")
+    shapes = []
+    for k in range(nplanes):
+        w, h, f, zero = struct.unpack_from("<IIII", head, 48 + 16 * k)
+        if zero:
+            raise DctqError("frame: a plane record's fourth word is not 0")
+        shapes.append((f, h, w))
+    if _frame_geometry(shapes, colour) != nblocks:
+        raise DctqError("frame: nblocks does not match the plane records")
+    if payload_bytes >= 1 << 32:
+        raise DctqError("frame: payload_bytes must stay below 2^32")
+    if buflen < total:
+        raise DctqError("frame: shorter than total_bytes")
+    starts, end = _frame_sections(header_bytes, nblocks, length_bytes, adaptive, payload_bytes)
+    if end > total:
+        raise DctqError("frame: a section ends past total_bytes")
+    if end != total:
+        raise DctqError("frame: total_bytes is not the end of the payload")
+    return {"quality": quality, "adaptive": bool(adaptive), "colour": bool(colour), "length_bytes": length_bytes,
+            "shapes": shapes, "nblocks": nblocks, "payload_bytes": payload_bytes, "starts": starts}
+
+
+def frame_pack(bytes, offsets, shapes, quality, adaptive=False, var_nums=None, colour=False, stream=None):
+    """A packed stream and what its decoder must know -> one uint8 device tensor, the container
+    "frame v1" (include/dct_amd.h; tools/frame_ref.py pack gives the same bytes).  bytes / offsets
+    as bits_pack or Plan.encode_bits_planes return them; shapes[k] is (F, H, W) or (H, W) of plane
+    k; quality and adaptive the plan's (quality is clamped to 1..100 as the plan clamps it);
+    var_nums (adaptive only) one int32 tensor per plane or one [N]; colour=True says the three
+    planes are rgb_to_ycbcr's.  The header is built on the host, the sections are device copies
+    into one allocation.  Reads the largest length and the total back (two syncs)."""
+    import struct
+    import torch
+    if not isinstance(bytes, torch.Tensor) or not bytes.is_cuda or bytes.dtype != torch.uint8 or not bytes.is_contiguous():
+        raise DctqError("bytes must be a contiguous uint8 tensor on a HIP device")
+    shapes = [(1, *map(int, s)) if len(s) == 2 else tuple(map(int, s)) for s in shapes]
+    if any(len(s) != 3 for s in shapes):
+        raise DctqError("shapes entries must be (F, H, W) or (H, W)")
+    nblocks = _frame_geometry(shapes, colour)
+    _need_byte_offsets(offsets, nblocks, bytes)
+    dev = bytes.device
+    sections = []
+    lengths, lb = block_lengths(offsets, stream=stream)
+    sections.append(lengths.view(torch.uint8))
+    first, total = (v & 0xFFFFFFFF for v in _read_back(offsets[[0, nblocks]], stream))
+    if first != 0 or total != bytes.numel():
+        raise DctqError(f"offsets run from {first} to {total}, bytes holds {bytes.numel()}")
+    if adaptive:
+        if var_nums is None:
+            raise DctqError("an adaptive container needs var_nums")
+        vn = torch.cat([v.reshape(-1) for v in var_nums]) if isinstance(var_nums, (list, tuple)) else var_nums
+        sections.append(_need(vn, nblocks, torch.int32, "var_nums", dev)[:nblocks].view(torch.uint8))
+    sections.append(bytes)
+    header_bytes = 48 + 16 * len(shapes)
+    starts, end = _frame_sections(header_bytes, nblocks, lb, bool(adaptive), bytes.numel())
+    head = bytearray(FRAME_MAGIC)
+    head += struct.pack("<IBBBBB7xQQQ", header_bytes, min(max(int(quality), 1), 100), int(bool(adaptive)), len(shapes),
+                        lb, int(bool(colour)), nblocks, bytes.numel(), end)
+    for f, h, w in shapes:
+        head += struct.pack("<IIII", w, h, f, 0)
+    out = torch.empty(end, dtype=torch.uint8, device=dev)
+    with _on_stream(stream):
+        out[:header_bytes].copy_(torch.frombuffer(head, dtype=torch.uint8))
+        for at, sec in zip(starts, sections):
+            out[at:at + sec.numel()].copy_(sec)
+            out[at + sec.numel():min(_align16(at + sec.numel()), end)].zero_()
+    return out
+
+
+def frame_unpack(buf, stream=None) -> dict:
+    """A frame v1 container -> its parts, everything checked on the host before anything is
+    decoded (DctqError for every rule of the format's refusal list).  buf: a uint8 device tensor,
+    or anything host-side with the buffer protocol (bytes, bytearray, a numpy array), which is
+    uploaded; a device tensor that does not start on a 16-byte boundary is copied first.  The
+    header is read back from the first 112 bytes at most; the offsets are rebuilt on the device
+    (block_offsets) and their total compared with payload_bytes (two syncs in all).  Returns a
+    dict: quality, adaptive, colour, shapes [(F, H, W)], offsets int32 [N+1], bytes (the whole
+    payload, a view into buf: what Plan.decode_bits takes with offsets) and var_nums (adaptive:
+    a list of int32 views into buf, one per plane; else None)."""
+    import torch
+    if isinstance(buf, torch.Tensor):
+        if not buf.is_cuda or buf.dtype != torch.uint8 or buf.dim() != 1:
+            raise DctqError("buf must be a one-dimensional uint8 tensor on a HIP device, or a host buffer")
+        with _on_stream(stream):
+            if not buf.is_contiguous() or buf.data_ptr() % 16:
+                buf = buf.clone(memory_format=torch.contiguous_format)
+    else:
+        host = bytearray(memoryview(buf).cast("B"))
+        if len(host) < 48:
+            raise DctqError("frame: shorter than the 48-byte fixed header")
+        with _on_stream(stream):
+            buf = torch.frombuffer(host, dtype=torch.uint8).to("cuda")
+    if buf.numel() < 48:
+        raise DctqError("frame: shorter than the 48-byte fixed header")
+    with _on_stream(stream):
+        head = buf[:_FRAME_HEAD].cpu().numpy().tobytes()
+    h = _frame_header(head, buf.numel())
+    n, lb, starts = h["nblocks"], h["length_bytes"], h["starts"]
+    lengths = buf[starts[0]:starts[0] + n * lb]
+    offsets = block_offsets(lengths if lb == 1 else lengths.view(torch.int16), stream=stream)
+    total = _read_back(offsets[n:], stream)[0] & 0xFFFFFFFF
+    if total != h["payload_bytes"]:
+        raise DctqError(f"frame: the lengths sum to {total}, payload_bytes says {h['payload_bytes']}")
+    var_nums = None
+    if h["adaptive"]:
+        vn = buf[starts[1]:starts[1] + 4 * n].view(torch.int32)
+        nbs = [f * (hh // 8) * (w // 8) for f, hh, w in h["shapes"]]
+        var_nums = list(torch.split(vn, nbs))
+    return {"quality": h["quality"], "adaptive": h["adaptive"], "colour": h["colour"], "shapes": h["shapes"],
+            "length_bytes": lb, "offsets": offsets, "bytes": buf[starts[-1]:starts[-1] + h["payload_bytes"]],
+            "var_nums": var_nums}
+
+
+_frame_plans = {}
+
+
+def _frame_plan(quality: int, adaptive: bool, device) -> "Plan":
+    """compress / decompress keep one Plan per (quality, adaptive, device)."""
+    import torch
+    key = (min(max(int(quality), 1), 100), bool(adaptive), torch.device(device).index or 0)
+    if key not in _frame_plans:
+        with torch.cuda.device(key[2]):
+            _frame_plans[key] = Plan(key[0], key[1])
+    return _frame_plans[key]
+
+
+def compress(src, quality: int = 50, adaptive: bool = False, subsampling: str = "420", bgr: bool = False, stream=None):
+    """Pixels -> one self-contained uint8 device tensor (frame v1) that decompress turns back
+    into pixels with nothing else to remember.  src: an RGB stack as rgb_desc takes it (through
+    rgb_to_ycbcr with `subsampling` and `bgr`; the container says colour), or a list of 1..4 u8
+    planes [F, H, W] / [H, W] (plain planes).  Non-adaptive plans run Plan.encode_bits_planes;
+    adaptive ones forward_quant_planes into one coefficient and one var_num buffer, rle_encode and
+    bits_pack, because the decoder needs the var_num of every block."""
+    import torch
+    colour = isinstance(src, torch.Tensor)
+    planes = list(rgb_to_ycbcr(src, subsampling, bgr=bgr, stream=stream)) if colour else list(src)
+    if not 1 <= len(planes) <= 4:
+        raise DctqError("compress needs an RGB stack or a list of 1..4 planes")
+    _same_device(planes, "planes")
+    descs = [plane_desc(p) for p in planes]
+    shapes = [(d.nframes, d.height, d.width) for d in descs]
+    plan = _frame_plan(quality, adaptive, planes[0].device)
+    var_nums = None
+    if adaptive:
+        nbs = [f * (h // 8) * (w // 8) for f, h, w in shapes]
+        coef = torch.empty((sum(nbs), 64), dtype=torch.int16, device=planes[0].device)
+        var_nums = torch.empty(sum(nbs), dtype=torch.int32, device=planes[0].device)
+        plan.forward_quant_planes(planes, outs=list(torch.split(coef, nbs)), var_nums=list(torch.split(var_nums, nbs)),
+                                  stream=stream)
+        off, sym = rle_encode(coef, stream=stream)
+        packed, boff = bits_pack(sym, off, stream=stream)
+    else:
+        _, boff, packed = plan.encode_bits_planes(planes, stream=stream)
+    return frame_pack(packed, boff, shapes, plan.quality, adaptive, var_nums, colour, stream=stream)
+
+
+def decompress(buf, channels: int = 3, planar: bool = False, bgr: bool = False, stream=None):
+    """The inverse of compress: frame_unpack, the container's plan, Plan.decode_bits and, for a
+    colour container, ycbcr_to_rgb (channels / planar / bgr as there).  Returns the RGB stack
+    [F, H, W, channels] for a colour container, the list of u8 planes [F, H, W] otherwise.
+    Nothing is decoded from a container that frame_unpack refuses."""
+    d = frame_unpack(buf, stream=stream)
+    plan = _frame_plan(d["quality"], d["adaptive"], d["bytes"].device)
+    outs = plan.decode_bits(d["bytes"], d["offsets"], shapes=d["shapes"], var_nums=d["var_nums"], stream=stream)
+    if not d["colour"]:
+        return outs
+    return ycbcr_to_rgb(*outs, channels=channels, planar=planar, bgr=bgr, stream=stream)
 
 
 def symbol_bytes(quality: int, adaptive: bool = False) -> int:

@@ -388,6 +388,42 @@ int dctq_bits_decode(const uint8_t *bytes, const uint32_t *offsets, long long nb
     return DCTQ_OK;
 }
 
+// the arguments the two frame entry points share: 1 <= nblocks <= 11 671 106 (368 * nblocks < 2^32, as dctq_bits_pack)
+static int frame_args(const void *offsets, const void *lengths, int length_bytes, long long nblocks) {
+    if (!offsets || !lengths) return fail(DCTQ_EINVAL, "offsets/lengths is NULL");
+    if (length_bytes != 1 && length_bytes != 2) return fail(DCTQ_EINVAL, "length_bytes must be 1 or 2");
+    if (nblocks < 1 || 368 * nblocks >= (1ll << 32)) return fail(DCTQ_EINVAL, "nblocks must be in [1, 11671106]");
+    if (((uintptr_t)offsets) % 4 || ((uintptr_t)lengths) % 4)
+        return fail(DCTQ_EINVAL, "offsets and lengths must be 4-byte aligned");
+    return DCTQ_OK;
+}
+
+int dctq_block_lengths(const uint32_t *offsets, long long nblocks, int length_bytes, void *lengths,
+                       uint32_t *max_length, void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryBlockLengths);
+    if (int rc = frame_args(offsets, lengths, length_bytes, nblocks)) return rc;
+    if (!max_length || ((uintptr_t)max_length) % 4) return fail(DCTQ_EINVAL, "max_length is NULL or not 4-byte aligned");
+    HIPCHK(dctq::launch_block_lengths(offsets, nblocks, length_bytes, lengths, max_length, (hipStream_t)stream,
+                                      device_cus()),
+           "block_lengths launch");
+    return DCTQ_OK;
+}
+
+size_t dctq_block_offsets_workspace_bytes(long long nblocks) {
+    return dctq::rle_workspace_bytes(nblocks < 1 ? 1 : nblocks);
+}
+
+int dctq_block_offsets(const void *lengths, int length_bytes, long long nblocks, uint32_t *offsets, void *workspace,
+                       void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryBlockOffsets);
+    if (int rc = frame_args(offsets, lengths, length_bytes, nblocks)) return rc;
+    if (!workspace) return fail(DCTQ_EINVAL, "workspace is NULL");
+    HIPCHK(dctq::launch_block_offsets(lengths, length_bytes, nblocks, offsets, workspace, (hipStream_t)stream,
+                                      device_cus()),
+           "block_offsets launch");
+    return DCTQ_OK;
+}
+
 int dctq_huffman_bits(const int16_t *coef, long long nblocks, uint32_t *bits, void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntryHuffmanBits);
     if (!coef || !bits) return fail(DCTQ_EINVAL, "coef/bits is NULL");

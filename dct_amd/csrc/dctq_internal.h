@@ -60,6 +60,8 @@ enum Entry : int {
     kEntryDecodeBitsPlanes,
     kEntryRgbToYcbcrPlanes,
     kEntryYcbcrToRgbPlanes,
+    kEntryBlockLengths,
+    kEntryBlockOffsets,
     kEntrySynchronize,
 };
 static_assert(kEntrySynchronize < 32, "LaunchIsolation keeps one bit per entry point in a uint32_t");
@@ -339,6 +341,11 @@ hipError_t launch_bits_decode(const uint8_t *bytes, const uint32_t *offsets, lon
                               hipStream_t stream, int num_cus);
 hipError_t launch_decode_bits(const SymbolSet &ss, const uint8_t *bytes, const uint32_t *offsets, const DevTables *dev,
                               int adaptive, bool inv_f32, hipStream_t stream, int num_cus);
+// byte offsets of a packed stream <-> one or two bytes of length per block (frame.hip); ws: rle_workspace_bytes(nblk)
+hipError_t launch_block_lengths(const uint32_t *offsets, long long nblk, int length_bytes, void *lengths,
+                                uint32_t *max_length, hipStream_t stream, int num_cus);
+hipError_t launch_block_offsets(const void *lengths, int length_bytes, long long nblk, uint32_t *offsets, void *ws,
+                                hipStream_t stream, int num_cus);
 // RGB <-> Y/Cb/Cr planes (color.hip); pixel_step 1, 3 or 4
 hipError_t launch_rgb_to_ycc(const ColorArgs &a, int pixel_step, bool s420, hipStream_t stream, int num_cus);
 hipError_t launch_ycc_to_rgb(const ColorArgs &a, int pixel_step, bool s420, hipStream_t stream, int num_cus);

@@ -312,6 +312,63 @@ int dctq_bits_decode(const uint8_t *bytes, const uint32_t *offsets, long long nb
 int dctq_decode_bits_planes(const dctq_plan *plan, const uint8_t *bytes, const uint32_t *offsets,
                             const int32_t *const *var_num, const dctq_plane *dst, int nplanes, void *stream);
 
+/* Self-contained container, format "frame v1": everything a decoder of a "bits
+ * v1" stream needs, in one byte buffer (tools/frame_ref.py states it in plain
+ * Python).  Little-endian.  A block of bits v1 is at most 368 B, so the N + 1
+ * uint32_t offsets hold no more than one byte of length per block (two when a
+ * block exceeds 255 B), and a scan on the device restores them.
+ *   Header, 48 + 16 * nplanes bytes:
+ *      0  8 B   magic "DCTQFRM1"
+ *      8  u32   header_bytes = 48 + 16 * nplanes
+ *     12  u8    quality, 1..100 (the plan's, after quant_init's clamp)
+ *     13  u8    adaptive, 0 or 1
+ *     14  u8    nplanes, 1..4
+ *     15  u8    length_bytes, 1 or 2
+ *     16  u8    colour: 0 = plain planes; 1 = the three planes are the Y, Cb, Cr
+ *               of dctq_rgb_to_ycbcr_planes (nplanes 3; Cb and Cr of one size,
+ *               plane 0's or half of it in both directions; equal nframes)
+ *     17..23    reserved, written 0; a reader refuses anything else
+ *     24  u64   nblocks = sum over the planes of nframes * (width / 8) *
+ *               (height / 8); 1 <= nblocks <= 11 671 106
+ *     32  u64   payload_bytes, < 2^32
+ *     40  u64   total_bytes, the container's length
+ *     48 + 16 k   4 x u32   plane k: width, height, nframes, 0; width and height
+ *               multiples of 8 and >= 8, nframes >= 1
+ *   Sections, each starting at the next multiple of 16 from the container's
+ *   first byte (padding written 0, ignored on read), in this order:
+ *     lengths   nblocks * length_bytes bytes: entry b = offsets[b+1] - offsets[b]
+ *               as u8 or u16;
+ *     var_num   4 * nblocks bytes of int32 in the concatenated block numbering,
+ *               present only when adaptive;
+ *     payload   payload_bytes bytes of bits v1.  total_bytes is its end.
+ *   Reading.  A length above 368 reads as 368 (with the nblocks limit a 32-bit
+ *   scan cannot wrap); offsets[0] = 0.  The sum of the lengths must equal
+ *   payload_bytes.  Offsets rebuilt from lengths are non-decreasing, which with
+ *   the sum check is the precondition under which bits v1 decodes any bytes
+ *   without reading outside the payload.
+ *   A reader refuses, before it decodes anything: a buffer shorter than 48 B,
+ *   than header_bytes or than total_bytes; a bad magic; a field out of range;
+ *   header_bytes or nblocks inconsistent with the plane records; a section that
+ *   ends past total_bytes; a lengths sum that differs from payload_bytes.
+ *
+ * dctq_block_lengths: lengths[b] = min(offsets[b+1] - offsets[b] (mod 2^32),
+ * 255 or 65535), nblocks entries of length_bytes (1 or 2) bytes each; nothing
+ * past the last entry is written.  max_length[0] = the largest unsaturated
+ * difference (written by the call; no initialisation needed), so the caller
+ * sees whether length_bytes sufficed.  offsets has nblocks + 1 entries.
+ * dctq_block_offsets: the inverse: offsets[0 .. nblocks] = exclusive prefix
+ * sums of min(length, 368); offsets[nblocks] = the total.  workspace: device
+ * memory of dctq_block_offsets_workspace_bytes(nblocks) bytes.
+ * Both: offsets, lengths and max_length 4-byte aligned; 1 <= nblocks <=
+ * 11 671 106 and length_bytes 1 or 2, else DCTQ_EINVAL, as for a NULL pointer.
+ * Asynchronous on stream; allocate nothing.  About 4 + length_bytes bytes moved
+ * per block. */
+int dctq_block_lengths(const uint32_t *offsets, long long nblocks, int length_bytes, void *lengths,
+                       uint32_t *max_length, void *stream);
+size_t dctq_block_offsets_workspace_bytes(long long nblocks);
+int dctq_block_offsets(const void *lengths, int length_bytes, long long nblocks, uint32_t *offsets,
+                       void *workspace, void *stream);
+
 /* Per-block Huffman size: bits[b] = what the reference's pipeline
  * reports for block b coded on its own (tests/test_entropy.c:329-341):
  * run_length_encode -> build_huffman_codes -> get_encoded_size
