@@ -11,6 +11,7 @@ The library is REQUIRED: importing a compute entry point without a built
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -89,6 +90,8 @@ def _bind(L: C.CDLL, diagnostic: bool) -> C.CDLL:
             "dctq_diag_inverse": ([vp, vp, vp, ll, vp, vp], i),
             "dctq_diag_plan_set_num_cus": ([vp, i], i),
             "dctq_diag_plan_set_inverse": ([vp, i], i),
+            "dctq_diag_set_grid_limit": ([i], i),
+            "dctq_diag_last_grid": ([C.POINTER(C.c_uint)], i),
             "dctq_debug_inverse_bound": ([i, i, C.POINTER(i)], C.c_double),
             "dctq_debug_symbol_bytes": ([i, i], i),
             "dctq_diag_legacy_lanes": ([C.POINTER(i), C.POINTER(i)], i),
@@ -112,8 +115,11 @@ def _bind(L: C.CDLL, diagnostic: bool) -> C.CDLL:
 
 
 def lib() -> C.CDLL:
-    """Load libdct_amd.so, the product library (fails loudly if it has not been built)."""
+    """Load libdct_amd.so, the product library (fails loudly if it has not been built).
+    Inside grid_limit (tests only) it is the diagnostic library instead: the limit lives there."""
     global _lib
+    if _grid_limited:
+        return diag()
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise DctqError(f"{LIB_PATH} is missing: run `python -m dct_amd.build` (hipcc, gfx950)")
@@ -131,6 +137,40 @@ def diag() -> C.CDLL:
             raise DctqError(f"{DIAG_PATH} is missing: run `python -m dct_amd.build` (hipcc, gfx950)")
         _diag = _bind(C.CDLL(DIAG_PATH), True)
     return _diag
+
+
+_grid_limited = False
+
+
+@contextlib.contextmanager
+def grid_limit(workgroups: int):
+    """TESTS ONLY: cap the grid of every persistent grid-stride launch at `workgroups` (1..65535;
+    dctq_diag_set_grid_limit), so a test-sized input gives each wave several tiles -- on the full
+    grid (256 CUs, multipliers of 32-64) a wave sees one tile up to about 16 M blocks.  The limit
+    lives in the diagnostic library, whose globals the product library does not share, so while
+    the context is active lib() is that library: every module-level wrapper (rle_*, bits_*,
+    block_*, huffman_bits, the colour conversions, frame_*, compress, decompress) and every Plan
+    created inside goes through it.  A Plan created outside keeps its own library and is not
+    limited.  On exit (also on an exception) the limit is 0 again; does not nest."""
+    global _grid_limited
+    if _grid_limited:
+        raise DctqError("grid_limit does not nest")
+    L = diag()
+    _check(L.dctq_diag_set_grid_limit(int(workgroups)), L)
+    _grid_limited = True
+    try:
+        yield
+    finally:
+        _grid_limited = False
+        L.dctq_diag_set_grid_limit(0)
+
+
+def last_grid() -> int:
+    """TESTS ONLY: the workgroups of this thread's most recent persistent launch through the
+    diagnostic library (dctq_diag_last_grid)."""
+    n = C.c_uint(0)
+    _check(diag().dctq_diag_last_grid(C.byref(n)), diag())
+    return int(n.value)
 
 
 def _check(rc: int, L: C.CDLL = None) -> None:
@@ -1027,9 +1067,9 @@ _frame_plans = {}
 
 
 def _frame_plan(quality: int, adaptive: bool, device) -> "Plan":
-    """compress / decompress keep one Plan per (quality, adaptive, device)."""
+    """compress / decompress keep one Plan per (quality, adaptive, device) and library (grid_limit)."""
     import torch
-    key = (min(max(int(quality), 1), 100), bool(adaptive), torch.device(device).index or 0)
+    key = (min(max(int(quality), 1), 100), bool(adaptive), torch.device(device).index or 0, _grid_limited)
     if key not in _frame_plans:
         with torch.cuda.device(key[2]):
             _frame_plans[key] = Plan(key[0], key[1])

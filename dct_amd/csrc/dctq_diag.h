@@ -38,6 +38,24 @@ int dctq_diag_plan_set_inverse(dctq_plan *plan, int mode);
  * batch of a 4K frame stack, so its row carry between batches runs only then). */
 int dctq_diag_plan_set_num_cus(dctq_plan *plan, int num_cus);
 
+/* Cap the grid of every persistent grid-stride launch made through THIS library
+ * instance (test-only): 0 = no limit, 1..65535 = at most that many workgroups,
+ * anything else DCTQ_EINVAL.  Every hot kernel is such a loop, and its grid is
+ * min(batches / waves, CUs x resident x multiplier): on 256 CUs with a multiplier
+ * of 64 a wave sees ONE tile up to about 16 M blocks, so without a limit no test-
+ * sized input runs a loop body twice -- the prefetched registers, the store drain
+ * before the next LDS read, the LDS stages a next tile overwrites.  Under a limit
+ * of 1 a 1 250-block picture gives each of the 4 waves five tiles.  It reaches the
+ * plan-less entry points too (dctq_rle_*, dctq_bits_*, dctq_block_*,
+ * dctq_huffman_bits, the colour conversions), which dctq_diag_plan_set_num_cus
+ * cannot.  Process-wide for this library, not per thread: tests set it, call,
+ * and set it back to 0.  libdct_amd.so has no setter, so its limit is always 0. */
+int dctq_diag_set_grid_limit(int workgroups);
+/* The grid (workgroups) of the calling thread's most recent persistent launch
+ * through this library (0 before the first): what a test asserts, so a limit that
+ * silently does nothing cannot pass. */
+int dctq_diag_last_grid(unsigned *workgroups);
+
 /* Moves exactly the bytes dctq_forward_quant_planes moves, in the access pattern
  * of its product kernel fdct8_quant_v3 (same grid, LDS footprint, prefetch, LDS
  * stage and 1 KiB stores) with no arithmetic.  coef[k] receives pixel bytes,

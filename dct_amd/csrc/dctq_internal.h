@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <optional>
 #include <type_traits>
 
@@ -95,8 +96,24 @@ inline int resident_per_cu(K kernel, int threads) {
     return nb;
 }
 
+// The diagnostic grid limit (isolation.hip; dctq_diag.h dctq_diag_set_grid_limit): 0 = none,
+// else the most workgroups any persistent grid-stride launch of this library instance gets,
+// so a test-sized input gives every wave several batches.  Only the diagnostic library
+// exports a setter: in the product it stays 0.  t_last_grid: the grid of the calling
+// thread's most recent such launch (dctq_diag_last_grid).
+extern std::atomic<uint32_t> g_grid_limit;
+extern thread_local uint32_t t_last_grid;
+// The grid a persistent grid-stride launch gets for the `grid` workgroups it asks for.
+inline uint32_t limited_grid(uint32_t grid) {
+    const uint32_t limit = g_grid_limit.load(std::memory_order_relaxed);
+    if (limit && grid > limit) grid = limit;
+    t_last_grid = grid;
+    return grid;
+}
+
 // The grid of a persistent grid-stride kernel over `nbatch` batches, one per wave and
-// step: a workgroup per `Waves` batches, at most `mult` x the resident workgroups.
+// step: a workgroup per `Waves` batches, at most `mult` x the resident workgroups (and
+// the diagnostic limit).
 // The occupancy is cached per kernel (the kernel is a template argument, so every
 // instantiation has its own static; thread-safe initialisation): every device this
 // library runs on is a gfx950.
@@ -105,7 +122,7 @@ inline uint32_t persistent_grid(uint64_t nbatch, int num_cus, int mult) {
     static const int per_cu = resident_per_cu(Kernel, Threads);
     const uint64_t want = (nbatch + Waves - 1) / Waves;
     const uint64_t cap = (uint64_t)num_cus * per_cu * mult;
-    return (uint32_t)(want < cap ? want : cap);
+    return limited_grid((uint32_t)(want < cap ? want : cap));
 }
 // ... and its launch; Mult is the kernel's own grid multiplier (kGridMult below).
 template <auto Kernel, int Threads, int Waves, int Mult, typename... A>

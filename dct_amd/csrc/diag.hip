@@ -291,6 +291,18 @@ int dctq_diag_plan_set_num_cus(dctq_plan *plan, int num_cus) {
     return DCTQ_OK;
 }
 
+int dctq_diag_set_grid_limit(int workgroups) {
+    if (workgroups < 0 || workgroups > 65535) return dctq::fail(DCTQ_EINVAL, "workgroups must be 0 (no limit) or 1..65535");
+    dctq::g_grid_limit.store((uint32_t)workgroups, std::memory_order_relaxed);
+    return DCTQ_OK;
+}
+
+int dctq_diag_last_grid(unsigned *workgroups) {
+    if (!workgroups) return dctq::fail(DCTQ_EINVAL, "NULL pointer");
+    *workgroups = dctq::t_last_grid;
+    return DCTQ_OK;
+}
+
 int dctq_diag_movement_planes(const dctq_plan *plan, const dctq_plane *planes, int nplanes, int16_t *const *coef,
                               void *stream) {
     DCTQ_ENTRY;

@@ -797,8 +797,8 @@ hipError_t launch_huffman_bits(const int16_t *coef, long long nblk, uint32_t *bi
     long long grid = (ntiles + kHufWaves - 1) / kHufWaves;
     const long long cap = (long long)num_cus * kHufGridPerCu;
     if (grid > cap) grid = cap;
-    hipLaunchKernelGGL(huffman_bits_kernel, dim3((unsigned)grid), dim3(kHufThreads), 0, stream, coef, nblk, bits,
-                       ntiles);
+    hipLaunchKernelGGL(huffman_bits_kernel, dim3(limited_grid((uint32_t)grid)), dim3(kHufThreads), 0, stream, coef,
+                       nblk, bits, ntiles);
     return hipGetLastError();
 }
 
@@ -881,6 +881,7 @@ hipError_t launch_huffman_from_pixels(const EncodeSet &es, const DevTables *dev,
     const long long cap = (long long)num_cus * kHufGridPerCu;  // a persistent grid (3 per CU) is +11 %
     if (grid > cap) grid = cap;
     if (grid < 1) return hipSuccess;
+    grid = limited_grid((uint32_t)grid);
     with_bools(
         [&](auto a) {
             hipLaunchKernelGGL(huffman_from_pixels_kernel<a>, dim3((unsigned)grid), dim3(kHufThreads), 0, stream, es, dev,

@@ -47,6 +47,9 @@ thread_local std::vector<SeenKey> t_seen;
 constexpr unsigned long long kNoId = ~0ull;
 }  // namespace
 
+std::atomic<uint32_t> g_grid_limit{0};  // dctq_internal.h limited_grid
+thread_local uint32_t t_last_grid = 0;
+
 bool runtime_started() { return g_runtime_up.load(std::memory_order_acquire); }
 void note_runtime_started() { g_runtime_up.store(true, std::memory_order_release); }
 

@@ -462,7 +462,7 @@ __global__ __launch_bounds__(kRleThreads, W == 4 ? 8 : 7) void rle_decode_kernel
 static unsigned grid_for(long long waves_wanted, int num_cus, int per_cu) {
     long long g = (waves_wanted + kRleWaves - 1) / kRleWaves;
     const long long cap = (long long)num_cus * per_cu;
-    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
+    return limited_grid((uint32_t)(g < 1 ? 1 : g > cap ? cap : g));  // and the diagnostic limit
 }
 
 // tile totals, then (16-B aligned) the segment sums

@@ -1894,6 +1894,18 @@ def test_huffman_bits_planes_many_batches_per_wave(T, dm):
         T.cuda.synchronize()
         bad = (got != want).nonzero()
         assert bad.numel() == 0, (kind, q, ad, cus, bad[:8].flatten().tolist())
+    # the same carry at a small shape: one workgroup (dct_amd.grid_limit), so 13 + 4 + 4 batches
+    # of a 4:2:0 stack are five or six per wave, plane changes inside every wave's sequence
+    planes = [dm.synth(51, "uniform", 136, 96, 4), dm.synth(52, "extreme", 72, 48, 4),
+              dm.synth(53, "smooth", 72, 48, 4)]
+    for q, ad in [(50, 0), (10, 1)]:
+        want = dm.huffman_bits(T.cat(dm.Plan(q, ad).forward_quant_planes(planes)))
+        with dm.grid_limit(1):
+            got = dm.Plan(q, ad).huffman_bits_planes(planes)
+            assert dm.last_grid() == 1
+        T.cuda.synchronize()
+        bad = (got != want).nonzero()
+        assert bad.numel() == 0, (q, ad, "grid_limit(1)", bad[:8].flatten().tolist())
 
 
 def test_encode_planes_fused(T, dm):
