@@ -221,42 +221,49 @@ int dctq_inverse(const dctq_plan *plan, const int16_t *coef, const int32_t *var_
     return DCTQ_OK;
 }
 
+// The destination planes of a decoder: pl[k] from dst[k], var[k] = var_num[k] for an adaptive plan (else NULL).
+// input(k): the caller's own checks of plane k's input, between the plane's and its var_num's.
+extern "C++" template <typename F>
+static int decoder_planes(const dctq_plan *plan, const int32_t *const *var_num, const dctq_plane *dst, int nplanes,
+                          dctq::PlaneArgs *pl, const int32_t **var, F &&input) {
+    if (nplanes < 1 || nplanes > dctq::kMaxPlanes) return fail(DCTQ_EINVAL, "nplanes must be in [1, 4]");
+    if (plan->adaptive && !var_num) return fail(DCTQ_EINVAL, "adaptive decode needs var_num");
+    for (int k = 0; k < nplanes; ++k) {
+        if (int rc = dctq::plane_args(&dst[k], &pl[k])) return rc;
+        if (int rc = input(k)) return rc;
+        if (plan->adaptive && !var_num[k]) return fail(DCTQ_EINVAL, "adaptive decode needs every var_num[k]");
+        var[k] = plan->adaptive ? var_num[k] : nullptr;
+    }
+    return DCTQ_OK;
+}
+
 int dctq_decode_planes(const dctq_plan *plan, const int16_t *const *coef, const int32_t *const *var_num,
                        const dctq_plane *dst, int nplanes, void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntryDecodePlanes);
     if (int rc = dctq::check_plan(plan)) return rc;
     if (!coef || !dst) return fail(DCTQ_EINVAL, "coef/dst is NULL");
-    if (nplanes < 1 || nplanes > dctq::kMaxPlanes) return fail(DCTQ_EINVAL, "nplanes must be in [1, 4]");
-    if (plan->adaptive && !var_num) return fail(DCTQ_EINVAL, "adaptive decode needs var_num");
     dctq::DecodeSet ds = {};
     ds.n = nplanes;
-    for (int k = 0; k < nplanes; ++k) {
-        if (int rc = dctq::plane_args(&dst[k], &ds.pl[k])) return rc;
+    const auto coef_of_plane = [&](int k) {
         if (!coef[k]) return fail(DCTQ_EINVAL, "coef[k] is NULL");
         if (((uintptr_t)coef[k]) % 16) return fail(DCTQ_EINVAL, "coef must be 16-byte aligned");
-        if (plan->adaptive && !var_num[k]) return fail(DCTQ_EINVAL, "adaptive decode needs every var_num[k]");
         ds.coef[k] = coef[k];
-        ds.var[k] = plan->adaptive ? var_num[k] : nullptr;
-    }
+        return (int)DCTQ_OK;
+    };
+    if (int rc = decoder_planes(plan, var_num, dst, nplanes, ds.pl, ds.var, coef_of_plane)) return rc;
     plane_batches(ds.pl, nplanes, 32, ds.first);
     HIPCHK(dctq::launch_decode(ds, plan->dev, plan->adaptive, plan->inv_f32 != 0, (hipStream_t)stream, plan->num_cus),
            "decode launch");
     return DCTQ_OK;
 }
 
-// The destination planes of the fused decoders: geometry, var_num and the concatenated block numbering.
+// The fused decoders' planes: decoder_planes and the concatenated block numbering.
 static int symbol_set(const dctq_plan *plan, const int32_t *const *var_num, const dctq_plane *dst, int nplanes,
                       dctq::SymbolSet *out) {
-    if (nplanes < 1 || nplanes > dctq::kMaxPlanes) return fail(DCTQ_EINVAL, "nplanes must be in [1, 4]");
-    if (plan->adaptive && !var_num) return fail(DCTQ_EINVAL, "adaptive decode needs var_num");
     dctq::SymbolSet &ss = *out;
     ss = {};
     ss.n = nplanes;
-    for (int k = 0; k < nplanes; ++k) {
-        if (int rc = dctq::plane_args(&dst[k], &ss.pl[k])) return rc;
-        if (plan->adaptive && !var_num[k]) return fail(DCTQ_EINVAL, "adaptive decode needs every var_num[k]");
-        ss.var[k] = plan->adaptive ? var_num[k] : nullptr;
-    }
+    if (int rc = decoder_planes(plan, var_num, dst, nplanes, ss.pl, ss.var, [](int) { return (int)DCTQ_OK; })) return rc;
     if (int rc = number_blocks(ss.pl, nplanes, ss.blk_first, 1ll << 26, "more than 2^26 - 1 blocks in one decode"))
         return rc;
     for (int k = nplanes + 1; k <= dctq::kMaxPlanes; ++k) ss.blk_first[k] = ss.blk_first[nplanes];

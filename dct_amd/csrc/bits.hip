@@ -4,7 +4,8 @@
 //
 //   dctq_bits_pack  : count (lane-per-block byte lengths, wave-scanned per 64-block tile),
 //                     the tile scan and fix-up of the symbol offsets (rle.hip), then emit.
-//   dctq_bits_decode: one wave per tile through bits_rebuild_half, rows out as 1 KiB stores.
+//   dctq_bits_decode: the decoders' tile loop (tile_decode_core.h) over bits_rebuild_half,
+//                     rows out as 1 KiB stores.
 //
 // A block's bits are serial, so both directions work lane-per-block; what the wave shares
 // is the memory side.  Emit: lane b packs block b into an LDS copy of the tile's bytes (the
@@ -14,7 +15,7 @@
 // finest quantizers) stores its bytes from the lanes directly.
 #include "bits_core.h"
 #include "scan_core.h"
-#include "zigzag.h"
+#include "tile_decode_core.h"
 
 namespace dctq {
 
@@ -155,37 +156,15 @@ __global__ __launch_bounds__(kBitsThreads) void bits_emit_kernel(const void *__r
     }
 }
 
-// ---- decode to coefficients: rows of the half tile as 1 KiB stores (8 lane-addresses per block)
+// ---- decode to coefficients: source = the packed bytes (bits_rebuild_half), sink = int16 rows
+// as 1 KiB stores; the loop, the sink and the hazard rule: tile_decode_core.h
 __global__ __launch_bounds__(kBitsThreads) void bits_to_coef(const uint8_t *__restrict__ bytes,
                                                              const uint32_t *__restrict__ offsets, long long nblk,
                                                              int16_t *__restrict__ coef, long long ntiles) {
-    __shared__ u4r wave_lds[kBitsWaves][kBitsLds / 16];
-    __shared__ uint8_t zz[64];
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (threadIdx.x < 64) zz[threadIdx.x] = kZigzag[threadIdx.x];
-    __syncthreads();
-    const long long stride = (long long)gridDim.x * kBitsWaves;
-    char *lt = reinterpret_cast<char *>(wave_lds[wv]);
-    uint8_t *lst = reinterpret_cast<uint8_t *>(lt + kHalf * kDecPitch);
-    for (long long t = (long long)blockIdx.x * kBitsWaves + wv; t < ntiles; t += stride) {
-        const long long b0 = t * 64;
-        const int nb = tile_blocks(t, nblk);
-        const uint32_t offv = offsets[b0 + (lane < nb ? lane : nb)];  // lanes >= nb: the end of the tile
-        const uint32_t oend = offsets[b0 + nb];
-        for (int h = 0; h < nb; h += kHalf) {
-            const int he = nb < h + kHalf ? nb : h + kHalf;
-            bits_rebuild_half(bytes, offv, oend, h, he, lane, lt, lst, zz);
-            u4r val[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                val[k] = *reinterpret_cast<const u4r *>(lt + (8 * k + (lane >> 3)) * kDecPitch + 16 * (lane & 7));
-            wave_sync_lds();  // every lane's rows are in registers before the next half zeroes the tile
-            const __amdgpu_buffer_rsrc_t rs =
-                __builtin_amdgcn_make_buffer_rsrc(coef + (b0 + h) * 64, (short)0, (he - h) * 128, kRsrcFlags);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) __builtin_amdgcn_raw_buffer_store_b128(val[k], rs, lane * 16, k * 1024, kNtAux);
-        }
-    }
+    decode_tiles<long long, kBitsWaves, kBitsLds>(
+        offsets, nblk, ntiles,
+        [&](auto... half) __attribute__((always_inline)) { return bits_rebuild_half(bytes, half...); },
+        [&](auto... half) __attribute__((always_inline)) { coef_rows_out<true>(coef, half...); });
 }
 
 hipError_t launch_bits_pack(const void *symbols, int symbol_bytes, const uint32_t *sym_offsets, long long nblk,

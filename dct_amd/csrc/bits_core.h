@@ -69,11 +69,13 @@ constexpr int kBitsLds = kHalf * kDecPitch + kBitsStage;
 static_assert(kBitsStage % 256 == 0 && kBitsStage - 3 >= 2 * 33 * 64 / 8, "whole load rounds; any block's useful bytes fit");
 
 // bytes: the stream; offv: lane b holds offsets[64t + b] (lanes >= nb: the tile's end); oend:
-// the tile's end.  Blocks [h, he) of the tile -> rows at lt + i * kDecPitch; lst: the stage
-// (kBitsStage bytes behind the half tile).  The caller follows with wave_sync_lds().
-__device__ __forceinline__ void bits_rebuild_half(const uint8_t *__restrict__ bytes, uint32_t offv, uint32_t oend,
-                                                  int h, int he, int lane, char *lt, uint8_t *lst,
-                                                  const uint8_t (&zz)[64]) {
+// the tile's end.  Blocks [h, he) of the tile -> rows at lt + i * kDecPitch (the pitch is
+// returned); the stage is the kBitsStage bytes behind the half tile.  A source of decode_tiles
+// (tile_decode_core.h), whose per-lane block lengths it does not need.
+__device__ __forceinline__ int bits_rebuild_half(const uint8_t *__restrict__ bytes, uint32_t offv, uint32_t oend,
+                                                 uint32_t /* cnt_lane */, int h, int he, int lane, char *lt,
+                                                 const uint8_t (*zz)[64]) {
+    uint8_t *lst = reinterpret_cast<uint8_t *>(lt + kHalf * kDecPitch);
     const int n = he - h;
     const uint32_t my_off = (uint32_t)__shfl((int)offv, (lane + h) & 63);
     const uint32_t nx_off = (uint32_t)__shfl((int)offv, (lane + h + 1) & 63);
@@ -144,7 +146,7 @@ __device__ __forceinline__ void bits_rebuild_half(const uint8_t *__restrict__ by
                 uint32_t r, m;
                 if (!get(r) || !get(m)) break;
                 pos += r;
-                const uint32_t at = pos < 64u ? 2u * zz[pos] : 128u;  // 128: the padding
+                const uint32_t at = pos < 64u ? 2u * (*zz)[pos] : 128u;  // 128: the padding
                 *reinterpret_cast<int16_t *>(row + at) = code_value(m);
                 pos += 1u;
             }
@@ -152,6 +154,7 @@ __device__ __forceinline__ void bits_rebuild_half(const uint8_t *__restrict__ by
         wave_sync_lds();  // the walk is done before the next chunk overwrites the stage
         s = e;
     }
+    return kDecPitch;
 }
 
 }  // namespace dctq

@@ -143,6 +143,13 @@ inline auto with_bools(F &&f, bool b0, B... rest) {
     return with_bools(
         [&](auto... c) { return b0 ? f(std::true_type(), c...) : f(std::false_type(), c...); }, rest...);
 }
+// f(ADAPTIVE, INV32) for a plan's inverse: the three legal leaves (0,0), (0,1), (1,0) -- the
+// fp32 inverse is the non-adaptive plans', so (1,1) is never instantiated.
+template <typename F>
+inline auto with_inverse(F &&f, bool adaptive, bool inv_f32) {
+    if (adaptive) return f(std::true_type(), std::false_type());
+    return inv_f32 ? f(std::false_type(), std::true_type()) : f(std::false_type(), std::false_type());
+}
 
 // Persistent grid-stride kernels launch kGridMult times their resident
 // workgroups; the extra ones queue and start as the first wave of workgroups
@@ -299,6 +306,20 @@ __device__ __forceinline__ int plane_of(const Set &ps, uint32_t g) {
 #pragma unroll
     for (int i = 1; i < kMaxPlanes; ++i) k += (i < ps.n && g >= ps.first[i]) ? 1 : 0;
     return k;
+}
+// Plane of block b < blk_first[kMaxPlanes] of a SymbolSet's concatenated numbering, and a
+// plane's first block (select chains: b and k may differ by lane).
+__device__ __forceinline__ int plane_of_block(const SymbolSet &ss, uint32_t b) {
+    int k = 0;
+#pragma unroll
+    for (int i = 1; i < kMaxPlanes; ++i) k += b >= ss.blk_first[i] ? 1 : 0;
+    return k;
+}
+__device__ __forceinline__ uint32_t block_first_of(const SymbolSet &ss, int k) {
+    uint32_t f = 0u;
+#pragma unroll
+    for (int i = 1; i < kMaxPlanes; ++i) f = k == i ? ss.blk_first[i] : f;
+    return f;
 }
 
 // The product forward (fdct8.hip): fdct8_quant_v3 over every plane of ps, every plan.

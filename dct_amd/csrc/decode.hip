@@ -83,16 +83,12 @@ __global__ __launch_bounds__(kThreadsP, 4) void decode8(DecodeSet ds, const DevT
 
 hipError_t launch_decode(const DecodeSet &ds, const DevTables *dev, int adaptive, bool inv_f32, hipStream_t stream,
                          int num_cus) {
-    return with_bools(
+    return with_inverse(
         [&](auto a, auto f32) {
-            if constexpr (a && f32) {
-                return hipErrorInvalidValue;  // never dispatched: the fp32 inverse is the non-adaptive plans'
-            } else {
-                return launch_persistent<decode8<a, f32>, kThreadsP, kWavesP, kDecodeGridMult>(
-                    ds.first[kMaxPlanes], num_cus, stream, ds, dev);
-            }
+            return launch_persistent<decode8<a, f32>, kThreadsP, kWavesP, kDecodeGridMult>(ds.first[kMaxPlanes],
+                                                                                         num_cus, stream, ds, dev);
         },
-        adaptive != 0, inv_f32 && !adaptive);
+        adaptive != 0, inv_f32);
 }
 
 }  // namespace dctq

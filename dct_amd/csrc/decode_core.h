@@ -1,9 +1,11 @@
 // dct_amd/csrc/decode_core.h -- the pixel sink of the decoders: a lane's four fp32 rows
 // of a half block clamped, rounded and packed to u8, and stored at their image position.
-// Shared by decode8 (decode.hip: coefficients in) and symbols_to_pixels
-// (decode_symbols.hip: run-length symbols in).
+// Shared by decode8 (decode.hip: coefficients in) and, with the read-out of the rebuilt rows
+// and the inverse in front of it (pixel_rows_out), by symbols_to_pixels and bits_to_pixels
+// (decode_symbols.hip, decode_bits.hip: a stream in).
 #pragma once
 #include "inverse_core.h"
+#include "rle_decode_core.h"
 
 namespace dctq {
 
@@ -45,6 +47,49 @@ __device__ __forceinline__ void store_pixel_rows(const PlaneArgs &p, uint32_t n,
 #pragma unroll
         for (int r = 0; r < 4; ++r) __builtin_nontemporal_store(pix[r], reinterpret_cast<u2p *>(px + r * p.stride));
     }
+}
+
+// The pixel sink of decode_tiles (tile_decode_core.h): blocks [b0 + h, b0 + he) of the planes
+// of ss, from the rows `rebuild` leaves in lt at pitch kDecPitch (four 16-B reads per lane
+// without bank conflicts), through decode8's paired-lane inverse.  A half can straddle
+// planes (the tiles run over the concatenated planes), so a block's plane, its number inside
+// the plane and its var_num are per lane.  The store descriptor is per plane and
+// wave-uniform: the wave loops over the planes present in the half (a wave-uniform range,
+// at most four) with the lanes of other planes masked off.
+template <bool ADAPTIVE, bool INV32, typename R>
+__device__ __forceinline__ void pixel_rows_out(const SymbolSet &ss, const DevTables *__restrict__ dev, uint32_t b0,
+                                               int h, int he, int lane, const char *lt, R &&rebuild) {
+    const int hh = lane >> 5, j = lane & 31;
+    // (a) lane (hh, j): block h + j of the tile; past the half's end, its last block (computed,
+    // not stored).  var_num is asked for ahead of the rebuild, which hides its latency
+    const uint32_t last = b0 + (uint32_t)he - 1u;
+    const bool valid = h + j < he;
+    const uint32_t gb = valid ? b0 + (uint32_t)(h + j) : last;
+    const int kl = plane_of_block(ss, gb);
+    const uint32_t n = gb - block_first_of(ss, kl);
+    int32_t vn = 0;
+    if (ADAPTIVE) vn = __builtin_nontemporal_load(var_of(ss, (uint32_t)kl) + n);
+
+    rebuild();
+    // (b) rows 4hh..4hh+3 of block j
+    uint4 cur[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const u4r v = *reinterpret_cast<const u4r *>(lt + j * kDecPitch + 16 * (4 * hh + r));
+        cur[r] = make_uint4(v[0], v[1], v[2], v[3]);
+    }
+    wave_sync_lds();  // every lane's rows are in registers before the next half zeroes the tile
+
+    // the whole wave runs the arithmetic (exec-masked scales and lane-half swaps inside)
+    u2p pix[4];
+    const auto pack = [&pix](int r, int c, const float (&o)[4]) { pix[r][c >> 2] = pack_u8x4(o[0], o[1], o[2], o[3]); };
+    if constexpr (INV32) inverse_half_f32_rows(dev, cur, hh, pack);
+    else inverse_half_rows<ADAPTIVE>(dev, cur, vn, hh, pack);
+
+    // the planes present in the half, one descriptor each
+    const int k_lo = __builtin_amdgcn_readfirstlane(plane_of_block(ss, b0 + (uint32_t)h));
+    const int k_hi = __builtin_amdgcn_readfirstlane(plane_of_block(ss, last));
+    for (int k = k_lo; k <= k_hi; ++k) store_pixel_rows(ss.pl[k], n, valid && kl == k, hh, pix);
 }
 
 }  // namespace dctq

@@ -153,16 +153,12 @@ __global__ __launch_bounds__(kThreads, kRtOcc) void distortion8(EncodeSet es, co
 
 hipError_t launch_distortion(const EncodeSet &es, const DevTables *dev, int adaptive, bool inv_f32, uint32_t *sse,
                              hipStream_t stream, int num_cus) {
-    return with_bools(
+    return with_inverse(
         [&](auto a, auto f32) {
-            if constexpr (a && f32) {
-                return hipErrorInvalidValue;  // never dispatched: the fp32 inverse is the non-adaptive plans'
-            } else {
-                return launch_persistent<distortion8<a, f32>, kThreads, kWaves, kRtGridMult>(
-                    es.ps.first[es.ps.n], num_cus, stream, es, dev, sse);
-            }
+            return launch_persistent<distortion8<a, f32>, kThreads, kWaves, kRtGridMult>(es.ps.first[es.ps.n], num_cus,
+                                                                                       stream, es, dev, sse);
         },
-        adaptive != 0, inv_f32 && !adaptive);
+        adaptive != 0, inv_f32);
 }
 
 }  // namespace dctq

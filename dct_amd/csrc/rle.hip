@@ -26,9 +26,8 @@
 //   dctq_rle_emit  : the symbols (one wave per tile, block by block).
 //   dctq_rle_decode: run_length_decode (:327-351) + zigzag_to_block (:183-210),
 //                    one wave per tile through a 64-entry LDS row.
-#include "rle_decode_core.h"
 #include "scan_core.h"
-#include "zigzag.h"
+#include "tile_decode_core.h"
 
 namespace dctq {
 
@@ -409,10 +408,9 @@ __global__ __launch_bounds__(kRleThreads, 4) void rle_emit_kernel(const int16_t 
     }
 }
 
-// ---- decode: one wave per 64-block tile, rebuilt 32 blocks at a time in a
-// natural-order LDS copy (rebuild_half, rle_decode_core.h: the lane, walk and quad
-// paths; 8 waves/SIMD) and written as 1 KiB stores (8 lane-addresses per block).
-// 4 KiB + 960 B per wave keeps 8 waves/SIMD (the scan path needs them).
+// ---- decode: source = the run-length symbols (rebuild_half, rle_decode_core.h: the lane,
+// walk and quad paths), sink = int16 rows as 1 KiB stores; the loop, the sink and the hazard
+// rule: tile_decode_core.h.  4 KiB + 960 B per wave keeps 8 waves/SIMD (the scan path needs them).
 constexpr int kDecLds = dec_lds_bytes(128);
 
 // (the 2-byte instantiation asks for 7 waves/SIMD: at 8 the register allocator spilled two
@@ -421,38 +419,10 @@ template <int W>
 __global__ __launch_bounds__(kRleThreads, W == 4 ? 8 : 7) void rle_decode_kernel(const void *__restrict__ symbols,
                                                                  const uint32_t *__restrict__ offsets, long long nblk,
                                                                  int16_t *__restrict__ coef, long long ntiles) {
-    __shared__ u4r wave_lds[kRleWaves][kDecLds / 16];
-    __shared__ uint8_t zz[64];
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (threadIdx.x < 64) zz[threadIdx.x] = kZigzag[threadIdx.x];
-    __syncthreads();
-    const long long stride = (long long)gridDim.x * kRleWaves;
-    char *lt = reinterpret_cast<char *>(wave_lds[wv]);
-    uint32_t *lsym = reinterpret_cast<uint32_t *>(lt + kHalf * 128);
-    for (long long t = (long long)blockIdx.x * kRleWaves + wv; t < ntiles; t += stride) {
-        const long long b0 = t * 64;
-        const int nb = tile_blocks(t, nblk);
-        const uint32_t offv = offsets[b0 + (lane < nb ? lane : nb)];  // lanes >= nb: the end of the tile
-        const uint32_t oend = offsets[b0 + nb];
-        // per-lane block symbol count (lane b: block b of the tile)
-        const uint32_t nxt_off = (uint32_t)__shfl_down((int)offv, 1);
-        const uint32_t cnt_lane = (lane == 63 ? oend : nxt_off) - offv;
-        for (int h = 0; h < nb; h += kHalf) {
-            const int he = nb < h + kHalf ? nb : h + kHalf;
-            const bool lane_path = rebuild_half<W, 128>(symbols, offv, oend, cnt_lane, h, he, lane, lt, lsym, zz);
-            wave_sync_lds();
-            retire_stores();  // vmcnt(0): the walk's last (clipped) loads before the read-out
-            u4r val[4];
-            const int pitch = lane_path ? 128 : kDecPitch;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                val[k] = *reinterpret_cast<const u4r *>(lt + (8 * k + (lane >> 3)) * pitch + 16 * (lane & 7));
-            const __amdgpu_buffer_rsrc_t rs =
-                __builtin_amdgcn_make_buffer_rsrc(coef + (b0 + h) * 64, (short)0, (he - h) * 128, kRsrcFlags);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) __builtin_amdgcn_raw_buffer_store_b128(val[k], rs, lane * 16, k * 1024, kNtAux);
-        }
-    }
+    decode_tiles<long long, kRleWaves, kDecLds>(
+        offsets, nblk, ntiles,
+        [&](auto... half) __attribute__((always_inline)) { return symbols_source<W, 128>(symbols, half...); },
+        [&](auto... half) __attribute__((always_inline)) { coef_rows_out<false>(coef, half...); });
 }
 
 // Grid = at most per_cu workgroups per CU (far more than are resident: the queued ones refill retiring
@@ -504,24 +474,25 @@ hipError_t launch_rle_emit(const int16_t *coef, long long nblk, const uint32_t *
     // 2-byte emit: up to 1 024 workgroups per CU (about one tile per wave on the bench step):
     // -2.3..-2.9 % on the encode step against 64 (round 6, profiles/r06/rle_grid_ab/, tools/enc_ab.py);
     // the 4-byte emit was 5 % slower that way (tools/rle_ab.py), and the decoders 5-17 %, so they keep 64
-    if (symbol_bytes == 2)
-        hipLaunchKernelGGL(rle_emit_kernel<2>, dim3(grid_for(ntiles, num_cus, 1024)), dim3(kRleThreads), 0, stream, coef,
-                           nblk, offsets, symbols, ntiles, capacity);
-    else
-        hipLaunchKernelGGL(rle_emit_kernel<4>, dim3(grid_for(ntiles, num_cus, 64)), dim3(kRleThreads), 0, stream, coef,
-                           nblk, offsets, symbols, ntiles, capacity);
+    with_bools(
+        [&](auto w2) {
+            hipLaunchKernelGGL(rle_emit_kernel<(decltype(w2)::value ? 2 : 4)>,
+                               dim3(grid_for(ntiles, num_cus, decltype(w2)::value ? 1024 : 64)), dim3(kRleThreads), 0,
+                               stream, coef, nblk, offsets, symbols, ntiles, capacity);
+        },
+        symbol_bytes == 2);
     return hipGetLastError();
 }
 
 hipError_t launch_rle_decode(const void *symbols, int symbol_bytes, const uint32_t *offsets, long long nblk,
                              int16_t *coef, hipStream_t stream, int num_cus) {
     const long long ntiles = (nblk + 63) / 64;
-    if (symbol_bytes == 2)
-        hipLaunchKernelGGL(rle_decode_kernel<2>, dim3(grid_for(ntiles, num_cus, 64)), dim3(kRleThreads), 0, stream,
-                           symbols, offsets, nblk, coef, ntiles);
-    else
-        hipLaunchKernelGGL(rle_decode_kernel<4>, dim3(grid_for(ntiles, num_cus, 64)), dim3(kRleThreads), 0, stream,
-                           symbols, offsets, nblk, coef, ntiles);
+    with_bools(
+        [&](auto w2) {
+            hipLaunchKernelGGL(rle_decode_kernel<(decltype(w2)::value ? 2 : 4)>, dim3(grid_for(ntiles, num_cus, 64)),
+                               dim3(kRleThreads), 0, stream, symbols, offsets, nblk, coef, ntiles);
+        },
+        symbol_bytes == 2);
     return hipGetLastError();
 }
 

@@ -29,7 +29,6 @@ __device__ __forceinline__ int tile_blocks(long long t, long long nblk) {
     const long long r = nblk - t * 64;
     return r < 0 ? 0 : r < 64 ? (int)r : 64;
 }
-
 typedef uint32_t u4r __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void wave_sync_lds() {

@@ -150,15 +150,16 @@ __global__ __launch_bounds__(kThreads, kRtOcc) void roundtrip8(RoundTripSet rt, 
 hipError_t launch_roundtrip(const RoundTripSet &rt, const DevTables *dev, int adaptive, bool inv_f32,
                             unsigned long long *fallbacks, hipStream_t stream, int num_cus) {
     return with_bools(
-        [&](auto a, auto v, auto s, auto f32) {
-            if constexpr (a && f32) {
-                return hipErrorInvalidValue;  // never dispatched: the fp32 inverse is the non-adaptive plans'
-            } else {
-                return launch_persistent<roundtrip8<a, v, s, f32>, kThreads, kWaves, kRtGridMult>(
-                    rt.ps.first[rt.ps.n], num_cus, stream, rt, dev, fallbacks);
-            }
+        [&](auto v, auto s) {
+            return with_inverse(
+                [&](auto a, auto f32) {
+                    return launch_persistent<roundtrip8<a, decltype(v)::value, decltype(s)::value, f32>, kThreads,
+                                             kWaves, kRtGridMult>(rt.ps.first[rt.ps.n], num_cus, stream, rt, dev,
+                                                                  fallbacks);
+                },
+                adaptive != 0, inv_f32);
         },
-        adaptive != 0, rt.ps.var[0] != nullptr, fallbacks != nullptr, inv_f32 && !adaptive);
+        rt.ps.var[0] != nullptr, fallbacks != nullptr);
 }
 
 }  // namespace dctq

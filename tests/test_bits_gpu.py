@@ -192,6 +192,57 @@ def test_decode_bits_equals_decode_symbols(T, dm, geo, q, ad):
     assert all(T.equal(a, w) for a, w in zip(again, want))
 
 
+# The four stream decoders share one tile loop, one coefficient sink and one pixel sink
+# (tile_decode_core.h, decode_core.h): the tail tile, the tail half and a half that straddles
+# planes, through all four at once.  One-frame planes of 8-pixel-high strips, N blocks in all:
+# around a half (31, 32, 33), around a tile (63, 64, 65) and past two (129); from 33 on, three
+# planes with one to three blocks in the middle one, placed so that one 32-block half holds
+# blocks of all three -- the first half, the second (65) or the third (129).
+TAIL_SPLITS = {1: [1], 31: [31], 32: [32], 33: [29, 2, 2], 63: [28, 3, 32], 64: [30, 1, 33], 65: [59, 3, 3],
+               129: [92, 3, 34]}
+# fp32 inverse; fp64 adaptive, 2-byte symbols allowed; fp64, 4-byte symbols only
+TAIL_PLANS = [(50, 0), (90, 1), (100, 0)]
+
+
+@pytest.mark.parametrize("q,ad", TAIL_PLANS)
+def test_tails_and_straddles_through_all_four_decoders(T, dm, q, ad):
+    plan = dm.Plan(q, ad)
+    assert widths_of(plan) == ([4] if q == 100 else [4, 2])
+    pad, gap = 8, 3
+    for total, split in TAIL_SPLITS.items():
+        shapes = [(1, 8, 8 * n) for n in split]
+        assert sum(nblocks(shapes)) == total
+        if len(split) == 3:  # some half [32i, 32i + 32) holds blocks of all three planes
+            lo, hi = split[0] - 1, split[0] + split[1]  # the last block of plane 0, the first of plane 2
+            assert lo // 32 == hi // 32 and 0 <= lo and hi < total, split
+        planes = synth_planes(dm, shapes, "uniform", seed=1400 + total)
+        vns = [T.zeros(nb, dtype=T.int32, device="cuda") for nb in split]
+        plan.forward_quant_planes(planes, var_nums=vns)
+        vns = vns if ad else None
+        pixels = None
+        for sb in widths_of(plan):
+            what = (q, ad, total, sb)
+            coefs, off, sym = plan.encode_planes(planes, symbol_bytes=sb)
+            forward = T.cat(coefs)
+            by, boff = dm.bits_pack(sym, off)
+            from_symbols, from_bits = dm.rle_decode(sym, off), dm.bits_decode(by, boff)
+            assert T.equal(from_symbols, forward), (what, "rle_decode(S) != the forward's coefficients")
+            assert T.equal(from_bits, forward), (what, "bits_decode(bits_pack(S)) != the forward's coefficients")
+            two = plan.decode_planes(split_planes(from_symbols, split), shapes=shapes, var_nums=vns)
+            for name, decode in (("decode_symbols", lambda v: plan.decode_symbols(sym, off, outs=v, var_nums=vns)),
+                                 ("decode_bits", lambda v: plan.decode_bits(by, boff, outs=v, var_nums=vns))):
+                bufs = [T.full((1, 8 + gap, s[2] + pad), SENTINEL, dtype=T.uint8, device="cuda") for s in shapes]
+                views = [b[:, :8, :s[2]] for b, s in zip(bufs, shapes)]
+                decode(views)
+                for k, s in enumerate(shapes):
+                    assert T.equal(views[k], two[k]), (what, name, k, int((views[k] != two[k]).sum()))
+                    bufs[k][:, :8, :s[2]] = SENTINEL
+                    assert bool((bufs[k] == SENTINEL).all()), (what, name, k, "bytes outside width x height written")
+            if pixels is not None:  # the pixels do not depend on the symbol format
+                assert all(T.equal(a, b) for a, b in zip(two, pixels)), what
+            pixels = two
+
+
 def test_dense_and_staged_paths(T, dm):
     """Extremes at q100: a half's bytes exceed the decoders' stage and a tile's the packer's, so
     the chunked decode and the direct emit run; smooth content at q50 is staged whole."""
