@@ -37,6 +37,38 @@ class _Rgb(C.Structure):
                 ("width", C.c_int), ("height", C.c_int), ("nframes", C.c_int)]
 
 
+class QuantContext(C.Structure):
+    """QuantContext of include/quantization.h (the reference's public layout)."""
+    _fields_ = [("block_size", C.c_int), ("quality", C.c_int), ("quant_matrix", C.POINTER(C.POINTER(C.c_double))),
+                ("dequant_matrix", C.POINTER(C.POINTER(C.c_double))), ("adaptive", C.c_int)]
+
+
+def _row_pointers(a):
+    """double ** over the rows of a C-contiguous float64 array [n, n] (no copy; the result keeps a alive)."""
+    rows = (C.POINTER(C.c_double) * a.shape[0])(*[C.cast(a[r].ctypes.data, C.POINTER(C.c_double))
+                                                  for r in range(a.shape[0])])
+    rows._array = a
+    return rows
+
+
+def quant_context(table, adaptive: bool = False, quality: int = 50, dequant=None, block_size: int = None) -> QuantContext:
+    """A QuantContext over the caller's memory: quant_matrix points at the rows of table (a
+    C-contiguous float64 numpy array [n, n], not copied, so later writes to it are writes to the
+    context), dequant_matrix at those of dequant, or NULL.  block_size defaults to n."""
+    import numpy as np
+    for a in (table, dequant):
+        if a is not None and not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.ndim == 2
+                                  and a.shape[0] == a.shape[1] and a.flags.c_contiguous):
+            raise ValueError("table and dequant must be C-contiguous float64 arrays [n, n]")
+    ctx = QuantContext(int(table.shape[0] if block_size is None else block_size), int(quality), None, None,
+                       int(bool(adaptive)))
+    ctx._rows = [_row_pointers(table), _row_pointers(dequant) if dequant is not None else None]
+    ctx.quant_matrix = C.cast(ctx._rows[0], C.POINTER(C.POINTER(C.c_double)))
+    if dequant is not None:
+        ctx.dequant_matrix = C.cast(ctx._rows[1], C.POINTER(C.POINTER(C.c_double)))
+    return ctx
+
+
 _lib = None
 _diag = None
 DIAG_PATH = os.path.join(HERE, "libdct_amd_diag.so")
@@ -46,6 +78,7 @@ def _bind(L: C.CDLL, diagnostic: bool) -> C.CDLL:
     vp, i, ll = C.c_void_p, C.c_int, C.c_longlong
     sig = {
         "dctq_plan_create": ([i, i, C.POINTER(vp)], i),
+        "dctq_plan_from_context": ([C.POINTER(QuantContext), C.POINTER(vp)], i),
         "dctq_plan_destroy": ([vp], None),
         "dctq_plan_set_fallback_counter": ([vp, vp], i),
         "dctq_forward_quant": ([vp, C.POINTER(_Plane), vp, vp, vp], i),
@@ -289,6 +322,42 @@ class Plan:
             if inverse not in ("fp64", "auto"):
                 raise DctqError('inverse must be "fp64" or "auto"')
             self._chk(self._L.dctq_diag_plan_set_inverse(h, 0 if inverse == "fp64" else 1))
+
+    @classmethod
+    def from_context(cls, ctx, diagnostic: bool = False):
+        """A plan bound to a reference-style context (dctq_plan_from_context): ctx is a
+        QuantContext (this module's ctypes structure of include/quantization.h) whose
+        quant_matrix rows the caller set.  Only block_size, quality, adaptive and the VALUES of
+        quant_matrix are read, and the values are copied before the call returns: plan.table is
+        the plan's read-only copy.  Anything the library refuses raises DctqError."""
+        import numpy as np
+        self = cls.__new__(cls)
+        self._L = diag() if diagnostic else lib()
+        self._diag = False
+        self._h = None
+        h = C.c_void_p()
+        self._chk(self._L.dctq_plan_from_context(C.byref(ctx) if ctx is not None else None, C.byref(h)))
+        self._h = h
+        self.quality, self.adaptive = int(ctx.quality), bool(ctx.adaptive)
+        self.table = np.array([[ctx.quant_matrix[r][c] for c in range(8)] for r in range(8)], dtype=np.float64)
+        self.table.setflags(write=False)
+        return self
+
+    @classmethod
+    def from_table(cls, table, adaptive: bool = False, quality: int = 50, diagnostic: bool = False):
+        """A plan of the caller's own quantization table: table holds the 8 x 8 doubles of a
+        QuantContext's quant_matrix, each in [1, 65535] (the library refuses anything else with
+        its invalid-argument error, DctqError).  The context handed to dctq_plan_from_context
+        has block_size 8, row pointers to the doubles, the given quality and adaptive, and a NULL
+        dequant_matrix: the library dequantizes with 1 / table, as the reference's
+        generate_dequant_matrix would.  quality is a label only (plan.quality); plan.table keeps
+        the values, and every method works as on a standard plan.  compress / decompress stay on
+        standard plans: the frame v1 header stores a quality, not a table."""
+        import numpy as np
+        t = np.ascontiguousarray(table, dtype=np.float64)
+        if t.size != 64:
+            raise ValueError("table must hold 8 x 8 entries")
+        return cls.from_context(quant_context(t.reshape(8, 8), adaptive, quality), diagnostic)
 
     def _chk(self, rc: int) -> None:
         _check(rc, self._L)

@@ -59,6 +59,9 @@ def _load_orc():
     lib.orc_forward_plane.argtypes = [_u8p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_int]
     lib.orc_inverse_plane.argtypes = [_i16p, C.c_void_p, C.c_int, C.c_int, C.c_int, _dp]
+    lib.orc_forward_plane_table.argtypes = [_u8p, C.c_long, C.c_int, C.c_int, _dp, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_int]
+    lib.orc_inverse_plane_table.argtypes = [_i16p, C.c_void_p, C.c_int, _dp, C.c_int, _dp]
     lib.orc_plane_variance.argtypes = [_u8p, C.c_long, C.c_int, C.c_int, _dp]
     lib.orc_splitmix.argtypes = [C.c_uint64, C.c_uint64]
     lib.orc_splitmix.restype = C.c_uint64
@@ -91,6 +94,69 @@ def ref_available() -> bool:
 _refs = {}
 
 
+def _pp(t):
+    return C.POINTER(C.POINTER(t))
+
+
+class _RefQuantContext(C.Structure):
+    """QuantContext of the reference's include/quantization.h."""
+    _fields_ = [("block_size", C.c_int), ("quality", C.c_int), ("quant_matrix", _pp(C.c_double)),
+                ("dequant_matrix", _pp(C.c_double)), ("adaptive", C.c_int)]
+
+
+def _rows(a, t):
+    """t ** over the rows of a C-contiguous numpy array [n, n] (no copy)."""
+    return C.cast((C.POINTER(t) * a.shape[0])(*[C.cast(a[r].ctypes.data, C.POINTER(t)) for r in range(a.shape[0])]),
+                  _pp(t))
+
+
+def _ref_table_call(lib, table, adaptive, var, src, dst, fwd):
+    """ref_driver.c's ref_quantize_table / ref_dequantize_table, step for step, through the
+    reference's own exported functions: quant_init(n, 50, adaptive), every entry of quant_matrix :=
+    table and of dequant_matrix := 1.0 / table, then quantize (fwd) or dequantize."""
+    n = table.shape[0]
+    ctx = lib.quant_init(n, 50, int(adaptive))
+    for i in range(n):
+        for j in range(n):
+            ctx.contents.quant_matrix[i][j] = table[i, j]
+            ctx.contents.dequant_matrix[i][j] = 1.0 / table[i, j]
+    if fwd:
+        lib.quantize(ctx, _rows(src, C.c_double), _rows(dst, C.c_int), var)
+    else:
+        lib.dequantize(ctx, _rows(src, C.c_int), _rows(dst, C.c_double), var)
+    lib.quant_free(ctx)
+
+
+def ref_quantize_table(table, adaptive: int, var: float, c, build: str = "O2") -> np.ndarray:
+    """The REFERENCE's quantize on a context whose public tables the caller overwrote (quant_matrix
+    := table, dequant_matrix := 1 / table): n x n doubles -> int32 [n * n].  ref_driver.c's entry
+    of the same name where the compiled library has it, else the same calls made from here."""
+    lib = ref(build)
+    t = np.ascontiguousarray(table, np.float64)
+    n = t.shape[0]
+    c = np.ascontiguousarray(c, np.float64).reshape(n, n)
+    q = np.zeros((n, n), np.int32)
+    if hasattr(lib, "ref_quantize_table"):
+        lib.ref_quantize_table(n, t.ravel(), int(adaptive), var, c.ravel(), q.ravel())
+    else:
+        _ref_table_call(lib, t, adaptive, var, c, q, True)
+    return q.ravel()
+
+
+def ref_dequantize_table(table, adaptive: int, var: float, q, build: str = "O2") -> np.ndarray:
+    """The REFERENCE's dequantize on the same context: n x n ints -> float64 [n * n]."""
+    lib = ref(build)
+    t = np.ascontiguousarray(table, np.float64)
+    n = t.shape[0]
+    q = np.ascontiguousarray(q, np.int32).reshape(n, n)
+    c = np.zeros((n, n), np.float64)
+    if hasattr(lib, "ref_dequantize_table"):
+        lib.ref_dequantize_table(n, t.ravel(), int(adaptive), var, q.ravel(), c.ravel())
+    else:
+        _ref_table_call(lib, t, adaptive, var, q, c, False)
+    return c.ravel()
+
+
 def ref(build: str = "O2"):
     """The compiled reference: oracle/_ref/libref.so (Justfile flags + -O2) or, with
     build="O0", oracle/_ref/libref_O0.so (the Justfile flags as they are: -g, -O0)."""
@@ -109,6 +175,19 @@ def ref(build: str = "O2"):
         lib.ref_variance.restype = C.c_double
         lib.ref_quantize.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, _dp, _ip]
         lib.ref_dequantize.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, _ip, _dp]
+        # a library compiled from an earlier ref_driver.c (it cannot be rebuilt where the reference's
+        # sources are absent) lacks these two: ref_quantize_table below then drives the same calls itself
+        if hasattr(lib, "ref_quantize_table"):
+            lib.ref_quantize_table.argtypes = [C.c_int, _dp, C.c_int, C.c_double, _dp, _ip]
+            lib.ref_dequantize_table.argtypes = [C.c_int, _dp, C.c_int, C.c_double, _ip, _dp]
+        lib.quant_init.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.quant_init.restype = C.POINTER(_RefQuantContext)
+        lib.quant_free.argtypes = [C.POINTER(_RefQuantContext)]
+        lib.quant_free.restype = None
+        lib.quantize.argtypes = [C.POINTER(_RefQuantContext), _pp(C.c_double), _pp(C.c_int), C.c_double]
+        lib.quantize.restype = None
+        lib.dequantize.argtypes = [C.POINTER(_RefQuantContext), _pp(C.c_int), _pp(C.c_double), C.c_double]
+        lib.dequantize.restype = None
         lib.ref_adjust.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, _dp]
         lib.ref_copy_to_coefficients.argtypes = [C.c_int, _dp, _ip]
         lib.ref_forward_plane.argtypes = [_u8p, C.c_int, C.c_int, C.c_int, C.c_int, _i16p, C.c_int, C.c_int]
@@ -186,32 +265,50 @@ def adjust(q: np.ndarray, var: float, is_quantize: int) -> np.ndarray:
     return m.reshape(n, n)
 
 
-def quantize(c: np.ndarray, quality: int, adaptive: int = 0, var: float = 0.0) -> np.ndarray:
+def _table(table, n: int = 8) -> np.ndarray:
+    """A caller's quantization table as the n * n contiguous doubles the C side reads."""
+    t = np.ascontiguousarray(table, dtype=np.float64).ravel()
+    if t.size != n * n:
+        raise ValueError("table must hold %d entries" % (n * n))
+    return t
+
+
+def quantize(c: np.ndarray, quality: int, adaptive: int = 0, var: float = 0.0, table=None) -> np.ndarray:
+    """table (n x n doubles), if given, replaces the table of `quality`."""
     n = c.shape[0]
     q = np.zeros(n * n, np.int32)
-    qm = quant_matrix(n, orc().orc_clamp_quality(quality)).ravel()
+    qm = quant_matrix(n, orc().orc_clamp_quality(quality)).ravel() if table is None else _table(table, n)
     orc().orc_quantize(n, qm, adaptive, var, np.ascontiguousarray(c, np.float64).ravel(), q)
     return q.reshape(n, n)
 
 
-def dequantize(q: np.ndarray, quality: int, adaptive: int = 0, var: float = 0.0) -> np.ndarray:
+def dequantize(q: np.ndarray, quality: int, adaptive: int = 0, var: float = 0.0, table=None) -> np.ndarray:
+    """table (n x n doubles), if given, replaces the table of `quality`; the dequantization
+    table is 1 / table either way."""
     n = q.shape[0]
     c = np.zeros(n * n)
-    dq = dequant_matrix(quant_matrix(n, orc().orc_clamp_quality(quality))).ravel()
+    qm = quant_matrix(n, orc().orc_clamp_quality(quality)) if table is None else _table(table, n).reshape(n, n)
+    dq = dequant_matrix(qm).ravel()
     orc().orc_dequantize(n, dq, adaptive, var, np.ascontiguousarray(q, np.int32).ravel(), c)
     return c.reshape(n, n)
 
 
 def forward_plane(px: np.ndarray, quality: int, adaptive: int = 0, nthreads: int = 8,
-                  want_float: bool = False):
-    """u8 plane [H, W] -> int16 [H/8 * W/8, 64] (and optionally float64 coefficients)."""
+                  want_float: bool = False, table=None):
+    """u8 plane [H, W] -> int16 [H/8 * W/8, 64] (and optionally float64 coefficients).
+    table (8 x 8 doubles), if given, is the quantization table instead of quant_matrix(8,
+    quality) -- a QuantContext whose quant_matrix the caller overwrote; quality is then unused."""
     px = np.ascontiguousarray(px, np.uint8)
     h, w = px.shape
     nb = (h // 8) * (w // 8)
     out = np.zeros((nb, 64), np.int16)
     fout = np.zeros((nb, 64), np.float64) if want_float else None
-    rc = orc().orc_forward_plane(px.ravel(), w, w, h, quality, adaptive, out.ctypes.data,
-                                 fout.ctypes.data if fout is not None else None, nthreads)
+    fp = fout.ctypes.data if fout is not None else None
+    if table is None:
+        rc = orc().orc_forward_plane(px.ravel(), w, w, h, quality, adaptive, out.ctypes.data, fp, nthreads)
+    else:
+        rc = orc().orc_forward_plane_table(px.ravel(), w, w, h, _table(table), adaptive, out.ctypes.data, fp,
+                                           nthreads)
     if rc != 0:
         raise ValueError("orc_forward_plane rc=%d" % rc)
     return (out, fout) if want_float else out
@@ -225,14 +322,22 @@ def plane_variance(px: np.ndarray) -> np.ndarray:
     return var
 
 
-def inverse_plane(coef: np.ndarray, quality: int, adaptive: int = 0, var=None) -> np.ndarray:
+def inverse_plane(coef: np.ndarray, quality: int, adaptive: int = 0, var=None, table=None) -> np.ndarray:
+    """int16 [nblk, 64] -> float64 [nblk, 64] = dct_inverse(dequantize(coef)) (no + 128).
+    table (8 x 8 doubles), if given, is the quantization table instead of quant_matrix(8,
+    quality); the reference's dequantization table for such a context is 1 / table (what
+    generate_dequant_matrix makes, src/quantization.c:101-111, and what dctq_plan_from_context
+    uses), so the non-adaptive multiplier is 1 / table and the adaptive one table * (2 - nv)."""
     coef = np.ascontiguousarray(coef, np.int16).reshape(-1, 64)
     recon = np.zeros(coef.shape, np.float64)
     v = None
     if var is not None:
         var = np.ascontiguousarray(var, np.float64)
         v = var.ctypes.data
-    orc().orc_inverse_plane(coef.ravel(), v, coef.shape[0], quality, adaptive, recon.ravel())
+    if table is None:
+        orc().orc_inverse_plane(coef.ravel(), v, coef.shape[0], quality, adaptive, recon.ravel())
+    else:
+        orc().orc_inverse_plane_table(coef.ravel(), v, coef.shape[0], _table(table), adaptive, recon.ravel())
     return recon
 
 

@@ -223,7 +223,7 @@ void orc_block_from_pixels(const uint8_t *px, long stride, int row0, int col0, i
 typedef struct {
     const uint8_t *px;
     long stride;
-    int bw, bh, quality, adaptive;
+    int bw, bh, adaptive;
     int16_t *out;
     double *fout; /* optional float-coefficient output [nblk][64] */
     int row_lo, row_hi;
@@ -252,8 +252,10 @@ static void *orc_thread(void *arg) {
     return NULL;
 }
 
-int orc_forward_plane(const uint8_t *px, long stride, int width, int height, int quality, int adaptive,
-                      int16_t *out, double *fout, int nthreads) {
+/* The plane loop with the 64 entries of the quantization table as given (what a
+ * caller-modified QuantContext holds); orc_forward_plane is this with the table of a quality. */
+int orc_forward_plane_table(const uint8_t *px, long stride, int width, int height, const double *table,
+                            int adaptive, int16_t *out, double *fout, int nthreads) {
     if (width % 8 || height % 8 || nthreads < 1) return -1;
     int bw = width / 8, bh = height / 8;
     if (nthreads > bh) nthreads = bh > 0 ? bh : 1;
@@ -266,14 +268,13 @@ int orc_forward_plane(const uint8_t *px, long stride, int width, int height, int
         jb->stride = stride;
         jb->bw = bw;
         jb->bh = bh;
-        jb->quality = orc_clamp_quality(quality);
         jb->adaptive = adaptive;
         jb->out = out;
         jb->fout = fout;
         jb->row_lo = (int)((long)bh * t / nthreads);
         jb->row_hi = (int)((long)bh * (t + 1) / nthreads);
         orc_dct_matrix(8, jb->d);
-        orc_quant_matrix(8, jb->quality, jb->q);
+        memcpy(jb->q, table, sizeof jb->q);
     }
     for (int t = 1; t < nthreads; ++t) pthread_create(&th[t], NULL, orc_thread, &jobs[t]);
     orc_rows(&jobs[0]);
@@ -283,16 +284,23 @@ int orc_forward_plane(const uint8_t *px, long stride, int width, int height, int
     return 0;
 }
 
+int orc_forward_plane(const uint8_t *px, long stride, int width, int height, int quality, int adaptive,
+                      int16_t *out, double *fout, int nthreads) {
+    double q[64];
+    orc_quant_matrix(8, orc_clamp_quality(quality), q);
+    return orc_forward_plane_table(px, stride, width, height, q, adaptive, out, fout, nthreads);
+}
+
 /* Inverse pipeline of tests/test_entropy.c:350-393 per block:
  * dequantize(q, var) -> dct_inverse -> recon = out + 128 (double, unclamped).
- * `var` per block is needed for adaptive mode (the forward pass's variance). */
-int orc_inverse_plane(const int16_t *coef, const double *var, int nblocks, int quality, int adaptive,
-                      double *recon) {
-    double d[64], q[64], dq[64], c[64], o[64];
+ * `var` per block is needed for adaptive mode (the forward pass's variance).
+ * The dequantization table is 1 / table (generate_dequant_matrix, src/quantization.c:101-111). */
+int orc_inverse_plane_table(const int16_t *coef, const double *var, int nblocks, const double *table,
+                            int adaptive, double *recon) {
+    double d[64], dq[64], c[64], o[64];
     int qi[64];
     orc_dct_matrix(8, d);
-    orc_quant_matrix(8, orc_clamp_quality(quality), q);
-    orc_dequant_matrix(8, q, dq);
+    orc_dequant_matrix(8, table, dq);
     for (long b = 0; b < nblocks; ++b) {
         for (int k = 0; k < 64; ++k) qi[k] = coef[b * 64 + k];
         orc_dequantize(8, dq, adaptive, var ? var[b] : 0.0, qi, c);
@@ -300,6 +308,13 @@ int orc_inverse_plane(const int16_t *coef, const double *var, int nblocks, int q
         for (int k = 0; k < 64; ++k) recon[b * 64 + k] = o[k];
     }
     return 0;
+}
+
+int orc_inverse_plane(const int16_t *coef, const double *var, int nblocks, int quality, int adaptive,
+                      double *recon) {
+    double q[64];
+    orc_quant_matrix(8, orc_clamp_quality(quality), q);
+    return orc_inverse_plane_table(coef, var, nblocks, q, adaptive, recon);
 }
 
 /* Per-block variance of a plane (adaptive side-channel for the inverse). */

@@ -21,6 +21,11 @@ int orc_forward_plane(const uint8_t *px, long stride, int width, int height, int
                       int16_t *out, double *fout, int nthreads);
 int orc_inverse_plane(const int16_t *coef, const double *var, int nblocks, int quality, int adaptive,
                       double *recon);
+/* the two plane drivers with the 64 entries of the quantization table as given */
+int orc_forward_plane_table(const uint8_t *px, long stride, int width, int height, const double *table,
+                            int adaptive, int16_t *out, double *fout, int nthreads);
+int orc_inverse_plane_table(const int16_t *coef, const double *var, int nblocks, const double *table,
+                            int adaptive, double *recon);
 int orc_plane_variance(const uint8_t *px, long stride, int width, int height, double *var);
 uint64_t orc_splitmix(uint64_t seed, uint64_t i);
 uint8_t orc_synth_pixel(uint64_t seed, int kind, int width, int x, int y);

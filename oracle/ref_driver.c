@@ -119,6 +119,43 @@ void ref_dequantize(int n, int quality, int adaptive, double var, const int *q, 
     quant_free(ctx);
 }
 
+/* quantize / dequantize on a context whose PUBLIC tables the caller set: quant_init(n,
+ * quality, adaptive), then every entry of ctx->quant_matrix := table and of
+ * ctx->dequant_matrix := 1.0 / table (what generate_dequant_matrix makes of it). */
+static QuantContext *ref_table_context(int n, int adaptive, const double *table) {
+    QuantContext *ctx = quant_init(n, 50, adaptive);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            ctx->quant_matrix[i][j] = table[i * n + j];
+            ctx->dequant_matrix[i][j] = 1.0 / table[i * n + j];
+        }
+    return ctx;
+}
+
+void ref_quantize_table(int n, const double *table, int adaptive, double var, const double *c, int *q) {
+    QuantContext *ctx = ref_table_context(n, adaptive, table);
+    double **a = alloc_array(n, n);
+    int **o = alloc_int_array(n, n);
+    to2d(c, a, n);
+    quantize(ctx, a, o, var);
+    for (int i = 0; i < n; ++i) memcpy(q + i * n, o[i], sizeof(int) * n);
+    free_array(a, n);
+    free_int_array(o, n);
+    quant_free(ctx);
+}
+
+void ref_dequantize_table(int n, const double *table, int adaptive, double var, const int *q, double *c) {
+    QuantContext *ctx = ref_table_context(n, adaptive, table);
+    int **a = alloc_int_array(n, n);
+    double **o = alloc_array(n, n);
+    for (int i = 0; i < n; ++i) memcpy(a[i], q + i * n, sizeof(int) * n);
+    dequantize(ctx, a, o, var);
+    from2d(o, c, n);
+    free_int_array(a, n);
+    free_array(o, n);
+    quant_free(ctx);
+}
+
 void ref_adjust(int n, int quality, double var, int is_quantize, double *m) {
     QuantContext *ctx = quant_init(n, quality, 1);
     double **r = adjust_matrix_for_block(ctx, var, is_quantize);

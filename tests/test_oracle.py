@@ -114,6 +114,61 @@ def test_oracle_vs_compiled_reference_random():
                 assert (qi == O.quantize(a.reshape(8, 8), q, ad, var).ravel()).all()
 
 
+def test_oracle_vs_compiled_reference_custom_tables():
+    """The oracle's table-taking paths against the compiled reference on a context whose public
+    tables the caller overwrote (quant_matrix := table, dequant_matrix := 1 / table), for every
+    table of tests/test_custom_tables_gpu.py, adaptive off and on: quantize / dequantize at
+    variances on both sides of both clamp edges of nv = min(1, max(0.1, var / 1000)), and the
+    plane drivers forward_plane / inverse_plane(table=...) block by block against
+    dct_forward -> calculate_block_variance -> quantize and dequantize -> dct_inverse."""
+    if not O.ref_available():
+        pytest.skip("oracle/_ref/libref.so not built here")
+    from test_custom_tables_gpu import tables
+    r = O.ref()
+    rng = np.random.default_rng(4242)
+    edges = [0.0, 99.999, 100.0, 100.001, 550.0, 999.999, 1000.0, 1000.001, 5000.0]
+    # 320 blocks of u8 pixels whose own variances lie on both sides of both edges (amplitudes 1 .. 127 about 128)
+    amp = np.resize(np.array([1, 4, 9, 12, 20, 30, 33, 50, 90, 127]), 320)
+    px = np.stack([rng.integers(128 - a, 128 + a + 1, (8, 8)) for a in amp]).astype(np.uint8)
+    plane = px.reshape(8, 40, 8, 8).transpose(0, 2, 1, 3).reshape(64, 320)  # block b at (b // 40, b % 40)
+    var = O.plane_variance(plane)
+    assert (var < 100).sum() > 30 and ((var > 100) & (var < 1000)).sum() > 30 and (var > 1000).sum() > 30
+    fwd = np.zeros((320, 64))
+    for b in range(320):
+        x = px[b].astype(np.float64) - 128.0
+        r.ref_forward(8, x.ravel().copy(), fwd[b])
+        assert r.ref_variance(8, x.ravel().copy()) == var[b]
+    for name, tab in tables().items():
+        for ad in (0, 1):
+            got_c = O.forward_plane(plane, 0, ad, table=tab)
+            got_r = O.inverse_plane(got_c, 0, ad, var if ad else None, table=tab)
+            for b in range(320):
+                rec = np.zeros(64)
+                qi = O.ref_quantize_table(tab, ad, var[b], fwd[b])
+                assert (qi == got_c[b]).all(), (name, ad, b)
+                dq = O.ref_dequantize_table(tab, ad, var[b], qi)
+                r.ref_inverse(8, dq, rec)
+                assert (rec.view(np.uint64) == got_r[b].view(np.uint64)).all(), (name, ad, b)
+                v = edges[b % len(edges)]
+                qi = O.ref_quantize_table(tab, ad, v, fwd[b])
+                assert (qi == O.quantize(fwd[b].reshape(8, 8), 0, ad, v, table=tab).ravel()).all(), (name, ad, b, v)
+                dq = O.ref_dequantize_table(tab, ad, v, qi)
+                want = O.dequantize(qi.reshape(8, 8), 0, ad, v, table=tab).ravel()
+                assert (dq.view(np.uint64) == want.view(np.uint64)).all(), (name, ad, b, v)
+
+
+def test_plane_drivers_with_the_table_of_a_quality():
+    """forward_plane / inverse_plane(quality) are the table-taking drivers with quant_matrix(8, quality)."""
+    plane = O.synth_plane(77, O.KINDS["smooth"], 64, 48)
+    var = O.plane_variance(plane)
+    for q in (1, 50, 100):
+        for ad in (0, 1):
+            c = O.forward_plane(plane, q, ad)
+            assert np.array_equal(c, O.forward_plane(plane, 0, ad, table=O.quant_matrix(8, q)))
+            a, b = O.inverse_plane(c, q, ad, var), O.inverse_plane(c, 0, ad, var, table=O.quant_matrix(8, q))
+            assert (a.view(np.uint64) == b.view(np.uint64)).all()
+
+
 def test_synth_kinds_are_distinct():
     a = [O.synth_plane(1, k, 64, 64) for k in range(4)]
     assert len({x.tobytes() for x in a}) == 4
