@@ -160,6 +160,7 @@ static int encode_planes(const dctq_plan *plan, const dctq_plane *planes, int np
     if (!offsets || !workspace) return fail(DCTQ_EINVAL, "offsets/workspace is NULL");
     if (symbols_capacity < 0) return fail(DCTQ_EINVAL, "symbols_capacity < 0");
     if (((uintptr_t)symbols) % 4) return fail(DCTQ_EINVAL, "symbols must be 4-byte aligned");
+    if (((uintptr_t)workspace) % 4) return fail(DCTQ_EINVAL, "workspace must be 4-byte aligned");
     if (symbol_bytes == 2 && plan->symbol_bytes != 2)
         return fail(DCTQ_EINVAL, "the plan's quantized coefficients can exceed 511: 2-byte symbols cannot hold them "
                                  "(dctq_plan_symbol_bytes == 4; use dctq_encode_planes)");
@@ -330,6 +331,7 @@ int dctq_rle_count(const int16_t *coef, long long nblocks, uint32_t *offsets, vo
     DCTQ_LAUNCH(stream, dctq::kEntryRleCount);
     if (int rc = rle_args(coef, offsets, nblocks)) return rc;
     if (!workspace) return fail(DCTQ_EINVAL, "workspace is NULL");
+    if (((uintptr_t)workspace) % 4) return fail(DCTQ_EINVAL, "workspace must be 4-byte aligned");
     HIPCHK(dctq::launch_rle_count(coef, nblocks, offsets, workspace, (hipStream_t)stream, device_cus()),
            "rle_count launch");
     return DCTQ_OK;
@@ -378,6 +380,7 @@ int dctq_bits_pack(const void *symbols, int symbol_bytes, const uint32_t *sym_of
     if (bytes_capacity < 0) return fail(DCTQ_EINVAL, "bytes_capacity < 0");
     if (((uintptr_t)symbols) % 4 || ((uintptr_t)sym_offsets) % 4 || ((uintptr_t)offsets) % 4 || ((uintptr_t)bytes) % 4)
         return fail(DCTQ_EINVAL, "symbols/sym_offsets/offsets/bytes must be 4-byte aligned");
+    if (((uintptr_t)workspace) % 4) return fail(DCTQ_EINVAL, "workspace must be 4-byte aligned");
     HIPCHK(dctq::launch_bits_pack(symbols, symbol_bytes, sym_offsets, nblocks, offsets, bytes,
                                   bytes ? (unsigned long long)bytes_capacity : 0ull, workspace, (hipStream_t)stream,
                                   device_cus()),
@@ -425,6 +428,7 @@ int dctq_block_offsets(const void *lengths, int length_bytes, long long nblocks,
     DCTQ_LAUNCH(stream, dctq::kEntryBlockOffsets);
     if (int rc = frame_args(offsets, lengths, length_bytes, nblocks)) return rc;
     if (!workspace) return fail(DCTQ_EINVAL, "workspace is NULL");
+    if (((uintptr_t)workspace) % 4) return fail(DCTQ_EINVAL, "workspace must be 4-byte aligned");
     HIPCHK(dctq::launch_block_offsets(lengths, length_bytes, nblocks, offsets, workspace, (hipStream_t)stream,
                                       device_cus()),
            "block_offsets launch");

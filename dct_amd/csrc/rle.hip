@@ -103,6 +103,8 @@ __global__ __launch_bounds__(kRleThreads) void rle_count_kernel(const int16_t *_
 constexpr int kScanThreads = 1024;
 constexpr int kScanPer = 8;
 constexpr int kSegTilesLog2 = 13;  // 1024 * 8 tiles per segment
+// four tile totals at a 4-byte aligned address (a workspace is the caller's, 4-byte aligned: include/dct_amd.h)
+typedef uint32_t u4s __attribute__((ext_vector_type(4), aligned(4)));
 
 __global__ __launch_bounds__(kScanThreads) void rle_scan_tiles_kernel(uint32_t *__restrict__ tiles, long long ntiles,
                                                                       uint32_t *__restrict__ segs) {
@@ -112,8 +114,8 @@ __global__ __launch_bounds__(kScanThreads) void rle_scan_tiles_kernel(uint32_t *
     const long long i0 = c0 + (long long)tid * kScanPer;
     uint32_t v[kScanPer];
     if (i0 + kScanPer <= ntiles) {
-        const uint4 a = *reinterpret_cast<const uint4 *>(tiles + i0), b = *reinterpret_cast<const uint4 *>(tiles + i0 + 4);
-        v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
+        const u4s a = *reinterpret_cast<const u4s *>(tiles + i0), b = *reinterpret_cast<const u4s *>(tiles + i0 + 4);
+        v[0] = a[0], v[1] = a[1], v[2] = a[2], v[3] = a[3], v[4] = b[0], v[5] = b[1], v[6] = b[2], v[7] = b[3];
     } else {
 #pragma unroll
         for (int i = 0; i < kScanPer; ++i) v[i] = i0 + i < ntiles ? tiles[i0 + i] : 0u;
@@ -139,8 +141,8 @@ __global__ __launch_bounds__(kScanThreads) void rle_scan_tiles_kernel(uint32_t *
         acc += v[i];
     }
     if (i0 + kScanPer <= ntiles) {
-        *reinterpret_cast<uint4 *>(tiles + i0) = make_uint4(out[0], out[1], out[2], out[3]);
-        *reinterpret_cast<uint4 *>(tiles + i0 + 4) = make_uint4(out[4], out[5], out[6], out[7]);
+        *reinterpret_cast<u4s *>(tiles + i0) = u4s{out[0], out[1], out[2], out[3]};
+        *reinterpret_cast<u4s *>(tiles + i0 + 4) = u4s{out[4], out[5], out[6], out[7]};
     } else {
 #pragma unroll
         for (int i = 0; i < kScanPer; ++i)
@@ -435,7 +437,7 @@ static unsigned grid_for(long long waves_wanted, int num_cus, int per_cu) {
     return limited_grid((uint32_t)(g < 1 ? 1 : g > cap ? cap : g));  // and the diagnostic limit
 }
 
-// tile totals, then (16-B aligned) the segment sums
+// tile totals, then (at a multiple of 16 B from the workspace's first byte) the segment sums
 size_t rle_scan_workspace_bytes(long long ntiles) { return (size_t)((ntiles + 3) / 4 * 4) * 4 + 128 * 4; }
 size_t rle_workspace_bytes(long long nblk) { return rle_scan_workspace_bytes((nblk + 63) / 64); }
 

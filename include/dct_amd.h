@@ -114,7 +114,8 @@ int dctq_round_trip_planes(const dctq_plan *plan, const dctq_plane *planes, int 
  * symbols_capacity are not written; offsets are always complete (compare
  * offsets[N] with the capacity).  symbols == NULL or capacity 0: coefficients
  * and offsets only.  Worst case 64 symbols per block.  symbols 4-byte aligned.
- * workspace: dctq_encode_workspace_bytes(N) bytes. */
+ * workspace: dctq_encode_workspace_bytes(N) bytes of device memory, 4-byte
+ * aligned; scratch (its contents after the call mean nothing). */
 size_t dctq_encode_workspace_bytes(long long total_blocks);
 int dctq_encode_planes(const dctq_plan *plan, const dctq_plane *planes, int nplanes, int16_t *const *coef,
                        uint32_t *offsets, uint32_t *symbols, long long symbols_capacity, void *workspace,
@@ -230,7 +231,7 @@ int dctq_decode_symbols_planes(const dctq_plan *plan, const void *symbols, int s
  * symbols, so the stream is built in two steps:
  *   dctq_rle_count: offsets[b] = symbols before block b, offsets[nblocks] =
  *                   total (nblocks + 1 entries); `workspace` is device memory
- *                   of dctq_rle_workspace_bytes(nblocks) bytes;
+ *                   of dctq_rle_workspace_bytes(nblocks) bytes, 4-byte aligned;
  *   dctq_rle_emit:  symbols[offsets[b] .. offsets[b+1]) for every block
  *                   (the caller sizes `symbols` from offsets[nblocks], or
  *                   64 * nblocks for the worst case).
@@ -285,7 +286,7 @@ int dctq_rle_decode(const uint32_t *symbols, const uint32_t *offsets, long long 
  * symbols.  For ANY symbol input
  *   dctq_bits_decode(dctq_bits_pack(S)) == dctq_rle_decode(S).
  * symbols, sym_offsets, offsets and bytes 4-byte aligned; workspace: device memory
- * of dctq_bits_workspace_bytes(nblocks) bytes; 1 <= nblocks < 2^26 and
+ * of dctq_bits_workspace_bytes(nblocks) bytes, 4-byte aligned; 1 <= nblocks < 2^26 and
  * 368 * nblocks < 2^32 (offsets are 32-bit: nblocks <= 11 671 106), else
  * DCTQ_EINVAL.  Four launches on stream (count, scan, fix-up, emit); allocates
  * nothing. */
@@ -358,7 +359,7 @@ int dctq_decode_bits_planes(const dctq_plan *plan, const uint8_t *bytes, const u
  * sees whether length_bytes sufficed.  offsets has nblocks + 1 entries.
  * dctq_block_offsets: the inverse: offsets[0 .. nblocks] = exclusive prefix
  * sums of min(length, 368); offsets[nblocks] = the total.  workspace: device
- * memory of dctq_block_offsets_workspace_bytes(nblocks) bytes.
+ * memory of dctq_block_offsets_workspace_bytes(nblocks) bytes, 4-byte aligned.
  * Both: offsets, lengths and max_length 4-byte aligned; 1 <= nblocks <=
  * 11 671 106 and length_bytes 1 or 2, else DCTQ_EINVAL, as for a NULL pointer.
  * Asynchronous on stream; allocate nothing.  About 4 + length_bytes bytes moved

@@ -330,18 +330,19 @@ def test_any_bytes_decode(T, dm):
 
 # ---- 5. capacity ----------------------------------------------------------------------------------------------
 def raw_pack(dm, T, sym, off, buf, cap, nblk=None, sb=None, boff=None, ws="ok", symbols="ok", sym_offsets="ok"):
-    """dctq_bits_pack as a C host calls it.  Returns (rc, byte offsets tensor)."""
+    """dctq_bits_pack as a C host calls it.  Returns (rc, byte offsets tensor).  ws: "ok", None (NULL) or a
+    number of bytes to add to the workspace's address."""
     L = dm.lib()
     n = off.numel() - 1 if nblk is None else nblk
     if boff is None:
         boff = T.full((off.numel(),), -1, dtype=T.int32, device="cuda")
-    wsp = T.empty(int(L.dctq_bits_workspace_bytes(off.numel() - 1)) // 4 + 1, dtype=T.int32, device="cuda")
+    wsp = T.empty(int(L.dctq_bits_workspace_bytes(off.numel() - 1)) // 4 + 2, dtype=T.int32, device="cuda")
     rc = L.dctq_bits_pack(C.c_void_p(sym.data_ptr()) if symbols == "ok" else symbols,
                           (2 if sym.dtype == T.int16 else 4) if sb is None else sb,
                           C.c_void_p(off.data_ptr()) if sym_offsets == "ok" else None, n,
                           C.c_void_p(boff.data_ptr()) if boff is not False else None,
                           buf if isinstance(buf, (C.c_void_p, type(None))) else C.c_void_p(buf.data_ptr()), cap,
-                          C.c_void_p(wsp.data_ptr()) if ws == "ok" else None, None)
+                          None if ws is None else C.c_void_p(wsp.data_ptr() + (0 if ws == "ok" else ws)), None)
     T.cuda.synchronize()
     return rc, boff
 
@@ -397,6 +398,8 @@ def test_pack_and_decode_refusals(T, dm):
         "368 * nblocks >= 2^32": dict(nblk=11671107),
         "capacity < 0": dict(cap=-1),
         "misaligned bytes": dict(buf=C.c_void_p(buf.data_ptr() + 1)),
+        "workspace + 1": dict(ws=1),
+        "workspace + 2": dict(ws=2),
     }
     for what, kw in bad.items():
         kw = dict(kw)

@@ -63,14 +63,15 @@ def random_lengths(n, width):
 
 # ---- 1. lengths -> offsets ------------------------------------------------------------------------------------
 def raw_offsets(dm, T, lengths, lb, n=None, out="ok", ws="ok", lengths_ptr="ok"):
-    """dctq_block_offsets as a C host calls it.  Returns (rc, offsets tensor with two sentinels after)."""
+    """dctq_block_offsets as a C host calls it.  Returns (rc, offsets tensor with two sentinels after).  ws: "ok",
+    None (NULL) or a number of bytes to add to the workspace's address."""
     L = dm.lib()
     n = lengths.numel() if n is None else n
     off = T.full((lengths.numel() + 3,), -1, dtype=T.int32, device="cuda")
-    wsp = T.empty(int(L.dctq_block_offsets_workspace_bytes(lengths.numel())) // 4 + 1, dtype=T.int32, device="cuda")
+    wsp = T.empty(int(L.dctq_block_offsets_workspace_bytes(lengths.numel())) // 4 + 2, dtype=T.int32, device="cuda")
     rc = L.dctq_block_offsets(C.c_void_p(lengths.data_ptr()) if lengths_ptr == "ok" else None, lb, n,
                               C.c_void_p(off.data_ptr()) if out == "ok" else None,
-                              C.c_void_p(wsp.data_ptr()) if ws == "ok" else None, None)
+                              None if ws is None else C.c_void_p(wsp.data_ptr() + (0 if ws == "ok" else ws)), None)
     T.cuda.synchronize()
     return rc, off
 
@@ -189,6 +190,7 @@ def test_refusals_of_the_c_entry_points(T, dm):
         assert bool((buf == SENTINEL).all()), lb
     lengths = T.ones(n, dtype=T.uint8, device="cuda")
     bad = {"NULL lengths": dict(lengths_ptr=None), "NULL offsets": dict(out=None), "NULL workspace": dict(ws=None),
+           "workspace + 1": dict(ws=1), "workspace + 2": dict(ws=2),
            "nblocks 0": dict(n=0), "nblocks past the limit": dict(n=MAX_BLOCKS + 1)}
     for what, kw in bad.items():
         rc, o = raw_offsets(dm, T, lengths, 1, **kw)

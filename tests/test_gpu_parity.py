@@ -1280,6 +1280,33 @@ def test_invalid_arguments(T, dm):
     assert L.dctq_huffman_bits_planes(plan._h, d, 1, None, None) != 0                     # bits NULL
     assert L.dctq_huffman_bits_planes(plan._h, d, 1, C.c_void_p(off.data_ptr() + 2), None) != 0  # misaligned
     assert L.dctq_huffman_bits_planes(None, d, 1, C.c_void_p(off.data_ptr()), None) != 0  # no plan
+    # a workspace is 4-byte aligned (include/dct_amd.h): workspace + 1 and + 2 are refused, nothing is launched
+    ws = torch.empty(int(L.dctq_encode_workspace_bytes(4)) // 4 + 2, dtype=torch.int32, device="cuda")
+    sym = torch.empty(4 * 64, dtype=torch.int32, device="cuda")
+    for fn, name in ((L.dctq_encode_planes, "dctq_encode_planes"), (L.dctq_encode_planes16, "dctq_encode_planes16")):
+        for delta in (1, 2):
+            off.fill_(-7)
+            o.fill_(-7)
+            assert fn(plan._h, d, 1, cp, C.c_void_p(off.data_ptr()), C.c_void_p(sym.data_ptr()), 4 * 64,
+                      C.c_void_p(ws.data_ptr() + delta), None) == -1, (name, delta)
+            assert b"workspace" in L.dctq_error_string(-1), (name, delta)
+            torch.cuda.synchronize()
+            assert bool((off == -7).all()) and bool((o == -7).all()), (name, delta, "a refused call wrote")
+        assert fn(plan._h, d, 1, cp, C.c_void_p(off.data_ptr()), C.c_void_p(sym.data_ptr()), 4 * 64,
+                  C.c_void_p(ws.data_ptr()), None) == 0, name   # the same call, unrefused
+        torch.cuda.synchronize()
+        assert off.tolist() == [0, 2, 4, 6, 8], name  # four constant blocks: the DC and the closing symbol each
+    wr = torch.empty(int(L.dctq_rle_workspace_bytes(4)) // 4 + 2, dtype=torch.int32, device="cuda")
+    o.zero_()
+    for delta in (1, 2):
+        off.fill_(-7)
+        assert L.dctq_rle_count(C.c_void_p(o.data_ptr()), 4, C.c_void_p(off.data_ptr()), C.c_void_p(wr.data_ptr() + delta),
+                                None) == -1, delta
+        torch.cuda.synchronize()
+        assert bool((off == -7).all()), (delta, "a refused dctq_rle_count wrote offsets")
+    assert L.dctq_rle_count(C.c_void_p(o.data_ptr()), 4, C.c_void_p(off.data_ptr()), C.c_void_p(wr.data_ptr()), None) == 0
+    torch.cuda.synchronize()
+    assert off.tolist() == [0, 1, 2, 3, 4]
 
 
 # ------------------------------------------------------------ legacy per-block API
