@@ -113,6 +113,9 @@ def _bind(L: C.CDLL, diagnostic: bool) -> C.CDLL:
         "dctq_distortion_planes": ([vp, C.POINTER(_Plane), i, vp, vp], i),
         "dctq_rgb_to_ycbcr_planes": ([C.POINTER(_Rgb), C.POINTER(_Plane), C.POINTER(_Plane), C.POINTER(_Plane), vp], i),
         "dctq_ycbcr_to_rgb_planes": ([C.POINTER(_Plane), C.POINTER(_Plane), C.POINTER(_Plane), C.POINTER(_Rgb), vp], i),
+        "dctq_rgb_to_ycbcr_pad_planes": ([C.POINTER(_Rgb), C.POINTER(_Plane), C.POINTER(_Plane), C.POINTER(_Plane), vp], i),
+        "dctq_ycbcr_to_rgb_crop_planes": ([C.POINTER(_Plane), C.POINTER(_Plane), C.POINTER(_Plane), C.POINTER(_Rgb), vp], i),
+        "dctq_pad_planes": ([C.POINTER(_Plane), C.POINTER(_Plane), i, vp], i),
         "dctq_stream_release": ([vp], i),
     }
     if diagnostic:
@@ -815,7 +818,9 @@ def rgb_desc(t, bgr: bool = False):
     3 or 4 is interleaved RGB / RGBX (a contiguous HWC tensor); unit pixel stride is planar (e.g.
     chw.permute(0, 2, 3, 1) of a contiguous [F, 3, H, W] tensor: channel stride H * W); rows and
     frames may be padded.  bgr=True describes the same memory with R and B exchanged (BGR / BGRX,
-    or the channel planes in reverse).  Strides the descriptor cannot express raise DctqError;
+    or the channel planes in reverse).  A stride that multiplies nothing is not looked at: a
+    one-pixel-wide tensor whose channel stride is 1 is read as interleaved, and the row stride of
+    a one-row tensor is taken as at least a row.  Strides the descriptor cannot express raise DctqError;
     alignment is the library's to check (include/dct_amd.h)."""
     import torch
     if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
@@ -828,6 +833,10 @@ def rgb_desc(t, bgr: bool = False):
         raise DctqError("rgb must be a tensor on a HIP device")
     f, h, w, c = t.shape
     sf, sh, sw, sc = t.stride()
+    if w == 1 and sw == 1 and sc == 1:  # one column of adjacent R, G, B: the pixel stride means nothing
+        sw = c
+    if h == 1:                          # one row: neither does the row stride
+        sh = max(sh, w * (1 if sw == 1 else sw))
     if sw == 1 and sc != 1:
         step, cs = 1, sc
     elif sc == 1 and sw in (3, 4) and c <= sw:
@@ -849,20 +858,26 @@ def _same_device(ts, what):
         raise DctqError(f"{what} must be on one device")
 
 
-def rgb_to_ycbcr(rgb, subsampling: str = "420", outs=None, bgr: bool = False, stream=None):
+def rgb_to_ycbcr(rgb, subsampling: str = "420", outs=None, bgr: bool = False, stream=None, pad: bool = False):
     """An RGB picture stack (rgb_desc(rgb, bgr)) -> (y, cb, cr) u8 planes in ONE launch
     (dctq_rgb_to_ycbcr_planes): y [F, H, W] and cb, cr [F, H/2, W/2] ("420") or [F, H, W]
     ("444"), ready for Plan.forward_quant_planes([y, cb, cr]) and Plan.encode_bits_planes.
     Exact integer BT.601 full range as tools/color_ref.py states it.  outs, if given, are the
-    three u8 tensors and may be strided views (bytes outside width x height are not touched)."""
+    three u8 tensors and may be strided views (bytes outside width x height are not touched).
+    pad=True (dctq_rgb_to_ycbcr_pad_planes) takes any size and any strides rgb_desc can express,
+    at any alignment: the picture is extended by edge replication to H', W', the next multiples
+    of 8 ("444") or 16 ("420"), and the planes are those of the extended picture
+    (color_ref.forward_padded)."""
     import torch
     d = rgb_desc(rgb, bgr)
     if subsampling not in ("420", "444"):
         raise DctqError('subsampling must be "420" or "444"')
     sub = 2 if subsampling == "420" else 1
-    if d.width % (8 * sub) or d.height % (8 * sub):
+    m = 8 * sub
+    if not pad and (d.width % m or d.height % m):
         raise DctqError(f"{subsampling}: width and height must be multiples of {8 * sub}, got {d.width} x {d.height}")
-    shapes = [(d.nframes, d.height, d.width)] + [(d.nframes, d.height // sub, d.width // sub)] * 2
+    eh, ew = -(-d.height // m) * m, -(-d.width // m) * m
+    shapes = [(d.nframes, eh, ew)] + [(d.nframes, eh // sub, ew // sub)] * 2
     if outs is None:
         outs = [torch.empty(s_, dtype=torch.uint8, device=rgb.device) for s_ in shapes]
     if len(outs) != 3:
@@ -872,24 +887,34 @@ def rgb_to_ycbcr(rgb, subsampling: str = "420", outs=None, bgr: bool = False, st
     for name, p, want in zip(("y", "cb", "cr"), descs, shapes):
         if (p.nframes, p.height, p.width) != want:
             raise DctqError(f"outs: {name} is {(p.nframes, p.height, p.width)}, {subsampling} of rgb needs {want}")
-    _check(lib().dctq_rgb_to_ycbcr_planes(C.byref(d), C.byref(descs[0]), C.byref(descs[1]), C.byref(descs[2]),
-                                          _stream_ptr(stream)))
+    fn = lib().dctq_rgb_to_ycbcr_pad_planes if pad else lib().dctq_rgb_to_ycbcr_planes
+    _check(fn(C.byref(d), C.byref(descs[0]), C.byref(descs[1]), C.byref(descs[2]), _stream_ptr(stream)))
     return tuple(outs)
 
 
-def ycbcr_to_rgb(y, cb, cr, out=None, channels: int = 3, planar: bool = False, bgr: bool = False, stream=None):
+def ycbcr_to_rgb(y, cb, cr, out=None, channels: int = 3, planar: bool = False, bgr: bool = False, stream=None,
+                 size=None):
     """(y, cb, cr) u8 planes (4:2:0 or 4:4:4, read from their shapes) -> an RGB picture stack in
     ONE launch (dctq_ycbcr_to_rgb_planes), the exact integer inverse of tools/color_ref.py.
     out None: allocates u8 [F, H, W, channels] (channels 3 or 4; the fourth byte is 255), or with
     planar=True [F, 3, H, W], returned as its [F, H, W, 3] view.  Otherwise writes into out as
     rgb_desc(out, bgr) describes it (strided views are fine: padding is not touched).  bgr=True
-    stores B where R would go and R where B would."""
+    stores B where R would go and R where B would.  size=(H, W) crops
+    (dctq_ycbcr_to_rgb_crop_planes; color_ref.inverse_cropped): the planes are those of a picture
+    extended to whole blocks, only its H x W pixels are written, and out, if given, is H x W at
+    any alignment."""
     import torch
     _same_device([y, cb, cr], "y, cb and cr")
     descs = [plane_desc(p) for p in (y, cb, cr)]
     f, h, w = descs[0].nframes, descs[0].height, descs[0].width
     if any(p.nframes != f for p in descs):
         raise DctqError("y, cb and cr differ in the number of frames")
+    if size is not None:
+        m = 8 if (descs[1].height, descs[1].width) == (h, w) else 16
+        ch, cw = int(size[0]), int(size[1])
+        if ch < 1 or cw < 1 or -(-ch // m) * m != h or -(-cw // m) * m != w:
+            raise DctqError(f"size {(ch, cw)} rounded up to multiples of {m} is not y's {(h, w)}")
+        h, w = ch, cw
     if out is None:
         if planar:
             out = torch.empty((f, 3, h, w), dtype=torch.uint8, device=y.device).permute(0, 2, 3, 1)
@@ -901,13 +926,41 @@ def ycbcr_to_rgb(y, cb, cr, out=None, channels: int = 3, planar: bool = False, b
     _same_device([y, out], "the planes and out")
     if (d.nframes, d.height, d.width) != (f, h, w):
         raise DctqError(f"out is {(d.nframes, d.height, d.width)} (F, H, W), y is {(f, h, w)}")
-    _check(lib().dctq_ycbcr_to_rgb_planes(C.byref(descs[0]), C.byref(descs[1]), C.byref(descs[2]), C.byref(d),
-                                          _stream_ptr(stream)))
+    fn = lib().dctq_ycbcr_to_rgb_planes if size is None else lib().dctq_ycbcr_to_rgb_crop_planes
+    _check(fn(C.byref(descs[0]), C.byref(descs[1]), C.byref(descs[2]), C.byref(d), _stream_ptr(stream)))
     return out
+
+
+def pad_planes(planes, outs=None, stream=None):
+    """1..4 u8 planes [F, H, W] / [H, W] of any size, strides and alignment -> their edge-padded
+    copies of ceil(H / 8) 8 x ceil(W / 8) 8 in ONE launch (dctq_pad_planes): out(x, y) =
+    plane(min(x, W - 1), min(y, H - 1)); a plane that is whole blocks already is copied.  outs, if
+    given, are u8 tensors of the padded sizes (strided views are fine: bytes outside them are
+    not touched).  Returns the list of padded planes, [F, H', W'] each."""
+    import torch
+    planes = list(planes)
+    if not 1 <= len(planes) <= 4:
+        raise DctqError("pad_planes needs 1..4 planes")
+    _same_device(planes, "planes")
+    src = [plane_desc(p) for p in planes]
+    shapes = [(d.nframes, -(-d.height // 8) * 8, -(-d.width // 8) * 8) for d in src]
+    if outs is None:
+        outs = [torch.empty(s_, dtype=torch.uint8, device=planes[0].device) for s_ in shapes]
+    if len(outs) != len(planes):
+        raise DctqError(f"outs needs one tensor per plane ({len(planes)}), got {len(outs)}")
+    _same_device([*planes, *outs], "planes and outs")
+    dst = [plane_desc(o) for o in outs]
+    for k, (d, want) in enumerate(zip(dst, shapes)):
+        if (d.nframes, d.height, d.width) != want:
+            raise DctqError(f"outs[{k}] is {(d.nframes, d.height, d.width)}, the padded plane is {want}")
+    n = len(planes)
+    _check(lib().dctq_pad_planes((_Plane * n)(*src), (_Plane * n)(*dst), n, _stream_ptr(stream)))
+    return [o if o.dim() == 3 else o.unsqueeze(0) for o in outs]
 
 
 # ---- the container "frame v1" (include/dct_amd.h, tools/frame_ref.py) -------------------------------
 FRAME_MAGIC = b"DCTQFRM1"
+FRAME_MAGIC_CROP = b"DCTQFRC1"   # the same with (pad_right | pad_bottom << 16) in each plane record's fourth word
 _FRAME_MAX_BLOCKS = 11_671_106   # 368 * nblocks < 2^32, as dctq_bits_pack
 _FRAME_HEAD = 48 + 16 * 4        # the longest header
 
@@ -993,6 +1046,20 @@ def _frame_geometry(shapes, colour) -> int:
     return n
 
 
+def _frame_crops(crops, shapes, colour):
+    """The rules of frame c1's fourth words for crops [(pad_bottom, pad_right)] per plane."""
+    if len(crops) != len(shapes):
+        raise DctqError("frame: crops needs one (pad_bottom, pad_right) per plane")
+    for k, ((pb, pr), (_, h, w)) in enumerate(zip(crops, shapes)):
+        most = 7
+        if colour:
+            most = 0 if k else (15 if shapes[1][1:] != shapes[0][1:] else 7)
+        if not (0 <= pb <= most and 0 <= pr <= most) or pr >= w or pb >= h:
+            raise DctqError(f"frame: plane {k}: pads {(pb, pr)} outside 0..{most} or not smaller than the plane")
+    if not any(pb or pr for pb, pr in crops):
+        raise DctqError("frame: the crop magic with no crop (that picture is frame v1)")
+
+
 def _frame_sections(header_bytes, nblocks, length_bytes, adaptive, payload_bytes):
     """(starts, total): where the lengths, (var_num) and payload sections start, and the payload's end."""
     at, starts = header_bytes, []
@@ -1009,8 +1076,9 @@ def _frame_header(head: bytes, buflen: int) -> dict:
     import struct
     if buflen < 48 or len(head) < 48:
         raise DctqError("frame: shorter than the 48-byte fixed header")
-    if head[:8] != FRAME_MAGIC:
+    if head[:8] not in (FRAME_MAGIC, FRAME_MAGIC_CROP):
         raise DctqError("frame: bad magic")
+    cropped = head[:8] == FRAME_MAGIC_CROP
     header_bytes, quality, adaptive, nplanes, length_bytes, colour = struct.unpack_from("<IBBBBB", head, 8)
     nblocks, payload_bytes, total = struct.unpack_from("<QQQ", head, 24)
     if not 1 <= quality <= 100 or adaptive > 1 or not 1 <= nplanes <= 4 or length_bytes not in (1, 2) or colour > 1:
@@ -1021,14 +1089,19 @@ def _frame_header(head: bytes, buflen: int) -> dict:
         raise DctqError("frame: header_bytes does not match nplanes")
     if buflen < header_bytes or len(head) < header_bytes:
         raise DctqError("frame: shorter than header_bytes")
-    shapes = []
+    shapes, words = [], []
     for k in range(nplanes):
-        w, h, f, zero = struct.unpack_from("<IIII", head, 48 + 16 * k)
-        if zero:
+        w, h, f, word = struct.unpack_from("<IIII", head, 48 + 16 * k)
+        if word and not cropped:
             raise DctqError("frame: a plane record's fourth word is not 0")
         shapes.append((f, h, w))
+        words.append(word)
     if _frame_geometry(shapes, colour) != nblocks:
         raise DctqError("frame: nblocks does not match the plane records")
+    crops = None
+    if cropped:
+        crops = [(word >> 16, word & 0xFFFF) for word in words]
+        _frame_crops(crops, shapes, colour)
     if payload_bytes >= 1 << 32:
         raise DctqError("frame: payload_bytes must stay below 2^32")
     if buflen < total:
@@ -1039,17 +1112,20 @@ def _frame_header(head: bytes, buflen: int) -> dict:
     if end != total:
         raise DctqError("frame: total_bytes is not the end of the payload")
     return {"quality": quality, "adaptive": bool(adaptive), "colour": bool(colour), "length_bytes": length_bytes,
-            "shapes": shapes, "nblocks": nblocks, "payload_bytes": payload_bytes, "starts": starts}
+            "shapes": shapes, "nblocks": nblocks, "payload_bytes": payload_bytes, "starts": starts, "crops": crops}
 
 
-def frame_pack(bytes, offsets, shapes, quality, adaptive=False, var_nums=None, colour=False, stream=None):
+def frame_pack(bytes, offsets, shapes, quality, adaptive=False, var_nums=None, colour=False, stream=None, crops=None):
     """A packed stream and what its decoder must know -> one uint8 device tensor, the container
     "frame v1" (include/dct_amd.h; tools/frame_ref.py pack gives the same bytes).  bytes / offsets
     as bits_pack or Plan.encode_bits_planes return them; shapes[k] is (F, H, W) or (H, W) of plane
     k; quality and adaptive the plan's (quality is clamped to 1..100 as the plan clamps it);
     var_nums (adaptive only) one int32 tensor per plane or one [N]; colour=True says the three
     planes are rgb_to_ycbcr's.  The header is built on the host, the sections are device copies
-    into one allocation.  Reads the largest length and the total back (two syncs)."""
+    into one allocation.  Reads the largest length and the total back (two syncs).  crops: per
+    plane (pad_bottom, pad_right), the rows and columns of the stored plane to drop after decoding;
+    with any of them non-zero the container is "frame c1" (magic DCTQFRC1), with None or all zero
+    it is frame v1, byte for byte."""
     import struct
     import torch
     if not isinstance(bytes, torch.Tensor) or not bytes.is_cuda or bytes.dtype != torch.uint8 or not bytes.is_contiguous():
@@ -1058,6 +1134,14 @@ def frame_pack(bytes, offsets, shapes, quality, adaptive=False, var_nums=None, c
     if any(len(s) != 3 for s in shapes):
         raise DctqError("shapes entries must be (F, H, W) or (H, W)")
     nblocks = _frame_geometry(shapes, colour)
+    if crops is not None:
+        crops = [(int(pb), int(pr)) for pb, pr in crops]
+        if len(crops) != len(shapes):
+            raise DctqError("frame: crops needs one (pad_bottom, pad_right) per plane")
+        if any(pb or pr for pb, pr in crops):
+            _frame_crops(crops, shapes, colour)
+        else:
+            crops = None
     _need_byte_offsets(offsets, nblocks, bytes)
     dev = bytes.device
     sections = []
@@ -1074,11 +1158,11 @@ def frame_pack(bytes, offsets, shapes, quality, adaptive=False, var_nums=None, c
     sections.append(bytes)
     header_bytes = 48 + 16 * len(shapes)
     starts, end = _frame_sections(header_bytes, nblocks, lb, bool(adaptive), bytes.numel())
-    head = bytearray(FRAME_MAGIC)
+    head = bytearray(FRAME_MAGIC if crops is None else FRAME_MAGIC_CROP)
     head += struct.pack("<IBBBBB7xQQQ", header_bytes, min(max(int(quality), 1), 100), int(bool(adaptive)), len(shapes),
                         lb, int(bool(colour)), nblocks, bytes.numel(), end)
-    for f, h, w in shapes:
-        head += struct.pack("<IIII", w, h, f, 0)
+    for (f, h, w), (pb, pr) in zip(shapes, crops or [(0, 0)] * len(shapes)):
+        head += struct.pack("<IIII", w, h, f, pr | pb << 16)
     out = torch.empty(end, dtype=torch.uint8, device=dev)
     with _on_stream(stream):
         out[:header_bytes].copy_(torch.frombuffer(head, dtype=torch.uint8))
@@ -1097,7 +1181,8 @@ def frame_unpack(buf, stream=None) -> dict:
     (block_offsets) and their total compared with payload_bytes (two syncs in all).  Returns a
     dict: quality, adaptive, colour, shapes [(F, H, W)], offsets int32 [N+1], bytes (the whole
     payload, a view into buf: what Plan.decode_bits takes with offsets) and var_nums (adaptive:
-    a list of int32 views into buf, one per plane; else None)."""
+    a list of int32 views into buf, one per plane; else None), and crops: None for frame v1, for
+    frame c1 the list of (pad_bottom, pad_right) per plane."""
     import torch
     if isinstance(buf, torch.Tensor):
         if not buf.is_cuda or buf.dtype != torch.uint8 or buf.dim() != 1:
@@ -1129,7 +1214,7 @@ def frame_unpack(buf, stream=None) -> dict:
         var_nums = list(torch.split(vn, nbs))
     return {"quality": h["quality"], "adaptive": h["adaptive"], "colour": h["colour"], "shapes": h["shapes"],
             "length_bytes": lb, "offsets": offsets, "bytes": buf[starts[-1]:starts[-1] + h["payload_bytes"]],
-            "var_nums": var_nums}
+            "var_nums": var_nums, "crops": h["crops"]}
 
 
 _frame_plans = {}
@@ -1151,13 +1236,26 @@ def compress(src, quality: int = 50, adaptive: bool = False, subsampling: str = 
     rgb_to_ycbcr with `subsampling` and `bgr`; the container says colour), or a list of 1..4 u8
     planes [F, H, W] / [H, W] (plain planes).  Non-adaptive plans run Plan.encode_bits_planes;
     adaptive ones forward_quant_planes into one coefficient and one var_num buffer, rle_encode and
-    bits_pack, because the decoder needs the var_num of every block."""
+    bits_pack, because the decoder needs the var_num of every block.
+    A source whose sides are not whole blocks (multiples of 8; of 16 for a 4:2:0 picture) is
+    edge-padded on the way in (rgb_to_ycbcr(pad=True), pad_planes) and the container is "frame
+    c1", which records what decompress crops; every other source takes the unpadded path and
+    gives frame v1."""
     import torch
     colour = isinstance(src, torch.Tensor)
-    planes = list(rgb_to_ycbcr(src, subsampling, bgr=bgr, stream=stream)) if colour else list(src)
-    if not 1 <= len(planes) <= 4:
-        raise DctqError("compress needs an RGB stack or a list of 1..4 planes")
-    _same_device(planes, "planes")
+    if colour:
+        d = rgb_desc(src, bgr)
+        m = 16 if subsampling == "420" else 8
+        crops = [(-d.height % m, -d.width % m), (0, 0), (0, 0)]
+        planes = list(rgb_to_ycbcr(src, subsampling, bgr=bgr, stream=stream, pad=any(crops[0])))
+    else:
+        planes = list(src)
+        if not 1 <= len(planes) <= 4:
+            raise DctqError("compress needs an RGB stack or a list of 1..4 planes")
+        _same_device(planes, "planes")
+        crops = [(-d.height % 8, -d.width % 8) for d in map(plane_desc, planes)]
+        if any(pb or pr for pb, pr in crops):
+            planes = pad_planes(planes, stream=stream)
     descs = [plane_desc(p) for p in planes]
     shapes = [(d.nframes, d.height, d.width) for d in descs]
     plan = _frame_plan(quality, adaptive, planes[0].device)
@@ -1172,20 +1270,26 @@ def compress(src, quality: int = 50, adaptive: bool = False, subsampling: str = 
         packed, boff = bits_pack(sym, off, stream=stream)
     else:
         _, boff, packed = plan.encode_bits_planes(planes, stream=stream)
-    return frame_pack(packed, boff, shapes, plan.quality, adaptive, var_nums, colour, stream=stream)
+    return frame_pack(packed, boff, shapes, plan.quality, adaptive, var_nums, colour, stream=stream, crops=crops)
 
 
 def decompress(buf, channels: int = 3, planar: bool = False, bgr: bool = False, stream=None):
     """The inverse of compress: frame_unpack, the container's plan, Plan.decode_bits and, for a
     colour container, ycbcr_to_rgb (channels / planar / bgr as there).  Returns the RGB stack
     [F, H, W, channels] for a colour container, the list of u8 planes [F, H, W] otherwise.
-    Nothing is decoded from a container that frame_unpack refuses."""
+    Nothing is decoded from a container that frame_unpack refuses.  A frame c1 container comes
+    back at its true size: the picture through ycbcr_to_rgb(size=(H, W)); plain planes as the
+    [:, :H, :W] VIEWS of the decoded (padded) planes, which are therefore not contiguous."""
     d = frame_unpack(buf, stream=stream)
     plan = _frame_plan(d["quality"], d["adaptive"], d["bytes"].device)
     outs = plan.decode_bits(d["bytes"], d["offsets"], shapes=d["shapes"], var_nums=d["var_nums"], stream=stream)
+    crops = d["crops"]
     if not d["colour"]:
-        return outs
-    return ycbcr_to_rgb(*outs, channels=channels, planar=planar, bgr=bgr, stream=stream)
+        if crops is None:
+            return outs
+        return [o[:, :o.shape[1] - pb, :o.shape[2] - pr] for o, (pb, pr) in zip(outs, crops)]
+    size = None if crops is None else (outs[0].shape[1] - crops[0][0], outs[0].shape[2] - crops[0][1])
+    return ycbcr_to_rgb(*outs, channels=channels, planar=planar, bgr=bgr, stream=stream, size=size)
 
 
 def symbol_bytes(quality: int, adaptive: bool = False) -> int:

@@ -552,6 +552,127 @@ int dctq_ycbcr_to_rgb_planes(const dctq_plane *y, const dctq_plane *cb, const dc
     return DCTQ_OK;
 }
 
+// The same for the padding entry points: the RGB stack is the true W x H picture at any
+// alignment, the planes are its extension to whole blocks.  *aligned: the picture needs neither
+// padding nor unaligned access, so color_args describes the same call.
+static int color_pad_args(const dctq_rgb *rgb, const dctq_plane *y, const dctq_plane *cb, const dctq_plane *cr,
+                          dctq::ColorPadArgs *out, int *pixel_step, bool *s420, bool *aligned) {
+    if (!rgb || !rgb->pixels) return fail(DCTQ_EINVAL, "rgb/pixels is NULL");
+    const int step = rgb->pixel_step;
+    if (step != 1 && step != 3 && step != 4) return fail(DCTQ_EINVAL, "pixel_step must be 1, 3 or 4");
+    const long long cs = rgb->channel_stride;
+    if (step == 1 ? cs == 0 : (cs != 1 && cs != -1))
+        return fail(DCTQ_EINVAL, "channel_stride must be +1 or -1 (interleaved) or non-zero (planar)");
+    if (rgb->width < 1 || rgb->height < 1 || rgb->nframes < 1)
+        return fail(DCTQ_EINVAL, "rgb: width, height and nframes must be >= 1");
+    dctq::PlaneArgs py, pb, pr;
+    if (int rc = dctq::plane_args(y, &py)) return rc;
+    if (int rc = dctq::plane_args(cb, &pb)) return rc;
+    if (int rc = dctq::plane_args(cr, &pr)) return rc;
+    if (cb->width != cr->width || cb->height != cr->height) return fail(DCTQ_EINVAL, "Cb and Cr differ in size");
+    const bool full = cb->width == y->width && cb->height == y->height;
+    const bool half = 2ll * cb->width == y->width && 2ll * cb->height == y->height;
+    if (!full && !half)
+        return fail(DCTQ_EINVAL, "chroma must be luma's size (4:4:4) or exactly half of it in both directions (4:2:0)");
+    const long long m = half ? 16 : 8;
+    if (y->width != (rgb->width + m - 1) / m * m || y->height != (rgb->height + m - 1) / m * m)
+        return fail(DCTQ_EINVAL, "the Y plane is not the RGB stack's size rounded up to whole blocks (8, or 16 in 4:2:0)");
+    if (rgb->nframes != y->nframes || cb->nframes != y->nframes || cr->nframes != y->nframes)
+        return fail(DCTQ_EINVAL, "the RGB stack and the planes differ in nframes");
+    if (rgb->stride < (long long)rgb->width * step) return fail(DCTQ_EINVAL, "rgb: stride smaller than one row");
+    if (rgb->nframes > 1 && rgb->frame_stride < rgb->stride * (long long)rgb->height)
+        return fail(DCTQ_EINVAL, "rgb: frame_stride smaller than one frame");
+    if (step == 1 && (cs < 0 ? -cs : cs) < rgb->width) return fail(DCTQ_EINVAL, "rgb: channel_stride smaller than one row");
+    const long long per_row = y->width / 8, per_frame = per_row * (y->height / (half ? 2 : 1));
+    if (per_frame * y->nframes >= (1ll << 31)) return fail(DCTQ_EINVAL, "2^31 patches or more in one call");
+    // the lowest byte of pixel (0,0): its B byte when the order is B, G, R
+    uint8_t *first = (uint8_t *)rgb->pixels - (step != 1 && cs == -1 ? 2 : 0);
+    dctq::ColorArgs &a = out->c;
+    a = {};
+    a.rgb = first;
+    a.rgb_stride = rgb->stride;
+    a.rgb_frame_stride = rgb->frame_stride;
+    a.channel_stride = cs;
+    a.swap = step != 1 && cs == -1;
+    a.y = const_cast<uint8_t *>(y->pixels), a.y_stride = y->stride, a.y_frame_stride = y->frame_stride;
+    a.cb = const_cast<uint8_t *>(cb->pixels), a.cb_stride = cb->stride, a.cb_frame_stride = cb->frame_stride;
+    a.cr = const_cast<uint8_t *>(cr->pixels), a.cr_stride = cr->stride, a.cr_frame_stride = cr->frame_stride;
+    a.npatch = (uint32_t)(per_frame * y->nframes);
+    a.per_row = (uint32_t)per_row;
+    a.per_frame = (uint32_t)per_frame;
+    a.div_row = dctq::make_fastdiv(a.per_row);
+    a.div_frame = dctq::make_fastdiv(a.per_frame);
+    out->width = (uint32_t)rgb->width;
+    out->height = (uint32_t)rgb->height;
+    *pixel_step = step;
+    *s420 = half;
+    *aligned = rgb->width == y->width && rgb->height == y->height && ((uintptr_t)first) % 4 == 0 &&
+               rgb->stride % 4 == 0 && rgb->frame_stride % 4 == 0 && (step != 1 || cs % 4 == 0);
+    return DCTQ_OK;
+}
+
+int dctq_rgb_to_ycbcr_pad_planes(const dctq_rgb *src, const dctq_plane *y, const dctq_plane *cb, const dctq_plane *cr,
+                                 void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryRgbToYcbcrPadPlanes);
+    dctq::ColorPadArgs a;
+    int step;
+    bool s420, aligned;
+    if (int rc = color_pad_args(src, y, cb, cr, &a, &step, &s420, &aligned)) return rc;
+    if (aligned)  // the same bytes from the kernels of the aligned entry point
+        HIPCHK(dctq::launch_rgb_to_ycc(a.c, step, s420, (hipStream_t)stream, device_cus()), "rgb_to_ycc launch");
+    else
+        HIPCHK(dctq::launch_rgb_to_ycc_pad(a, step, s420, (hipStream_t)stream, device_cus()), "rgb_to_ycc_pad launch");
+    return DCTQ_OK;
+}
+
+int dctq_ycbcr_to_rgb_crop_planes(const dctq_plane *y, const dctq_plane *cb, const dctq_plane *cr, const dctq_rgb *dst,
+                                  void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryYcbcrToRgbCropPlanes);
+    dctq::ColorPadArgs a;
+    int step;
+    bool s420, aligned;
+    if (int rc = color_pad_args(dst, y, cb, cr, &a, &step, &s420, &aligned)) return rc;
+    if (aligned)
+        HIPCHK(dctq::launch_ycc_to_rgb(a.c, step, s420, (hipStream_t)stream, device_cus()), "ycc_to_rgb launch");
+    else
+        HIPCHK(dctq::launch_ycc_to_rgb_crop(a, step, s420, (hipStream_t)stream, device_cus()), "ycc_to_rgb_crop launch");
+    return DCTQ_OK;
+}
+
+int dctq_pad_planes(const dctq_plane *src, const dctq_plane *dst, int nplanes, void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryPadPlanes);
+    if (!src || !dst) return fail(DCTQ_EINVAL, "src/dst is NULL");
+    if (nplanes < 1 || nplanes > dctq::kMaxPlanes) return fail(DCTQ_EINVAL, "nplanes must be 1..4");
+    dctq::PadSet ps = {};
+    ps.n = nplanes;
+    for (int k = 0; k < nplanes; ++k) {
+        const dctq_plane &s = src[k], &d = dst[k];
+        dctq::PlaneArgs pd;
+        if (int rc = dctq::plane_args(&d, &pd)) return rc;
+        if (!s.pixels) return fail(DCTQ_EINVAL, "src: pixels is NULL");
+        if (s.width < 1 || s.height < 1 || s.nframes < 1) return fail(DCTQ_EINVAL, "src: width, height and nframes must be >= 1");
+        if (s.stride < s.width) return fail(DCTQ_EINVAL, "src: stride smaller than one row");
+        if (s.nframes > 1 && s.frame_stride < s.stride * (long long)s.height)
+            return fail(DCTQ_EINVAL, "src: frame_stride smaller than one frame");
+        if (d.width != (s.width + 7) / 8 * 8 || d.height != (s.height + 7) / 8 * 8 || d.nframes != s.nframes)
+            return fail(DCTQ_EINVAL, "dst must be src's size rounded up to multiples of 8, with its nframes");
+        for (int j = 0; j < nplanes; ++j)
+            if (src[j].pixels == d.pixels) return fail(DCTQ_EINVAL, "src == dst: padding in place is not supported");
+        const long long per_row = d.width / 8, per_frame = per_row * d.height;
+        if (per_frame * d.nframes >= (1ll << 31)) return fail(DCTQ_EINVAL, "2^31 patches or more in one plane");
+        dctq::PadPlane &p = ps.pl[k];
+        p.src = s.pixels, p.src_stride = s.stride, p.src_frame_stride = s.frame_stride;
+        p.dst = const_cast<uint8_t *>(d.pixels), p.dst_stride = d.stride, p.dst_frame_stride = d.frame_stride;
+        p.width = (uint32_t)s.width, p.height = (uint32_t)s.height;
+        p.per_row = (uint32_t)per_row, p.per_frame = (uint32_t)per_frame;
+        p.npatch = (uint32_t)(per_frame * d.nframes);
+        p.div_row = dctq::make_fastdiv(p.per_row);
+        p.div_frame = dctq::make_fastdiv(p.per_frame);
+    }
+    HIPCHK(dctq::launch_pad_planes(ps, (hipStream_t)stream, device_cus()), "pad_planes launch");
+    return DCTQ_OK;
+}
+
 int dctq_device_count(int *count) {
     DCTQ_ENTRY;
     HIPCHK(hipGetDeviceCount(count), "hipGetDeviceCount");

@@ -64,8 +64,11 @@ enum Entry : int {
     kEntryBlockLengths,
     kEntryBlockOffsets,
     kEntrySynchronize,
+    kEntryRgbToYcbcrPadPlanes,
+    kEntryYcbcrToRgbCropPlanes,
+    kEntryPadPlanes,
 };
-static_assert(kEntrySynchronize < 32, "LaunchIsolation keeps one bit per entry point in a uint32_t");
+static_assert(kEntryPadPlanes < 32, "LaunchIsolation keeps one bit per entry point in a uint32_t");
 class LaunchIsolation {
   public:
     LaunchIsolation(const void *stream, Entry entry);
@@ -272,6 +275,27 @@ struct ColorArgs {
     FastDiv div_row, div_frame;  // by per_row and by per_frame
 };
 
+// The padding colour kernels' arguments (color_pad.hip): c describes the RGB stack (any
+// alignment) and the planes of the EXTENDED picture, over which the patches are numbered;
+// width x height is the true picture.
+struct ColorPadArgs {
+    ColorArgs c;
+    uint32_t width, height;
+};
+// dctq_pad_planes (color_pad.hip): plane k's w x h source (any alignment) and its destination of
+// per_row * 8 columns; a patch is 8 pixels of one destination row, npatch of them < 2^31.
+struct PadPlane {
+    const uint8_t *src;
+    uint8_t *dst;
+    long long src_stride, src_frame_stride, dst_stride, dst_frame_stride;
+    uint32_t width, height, npatch, per_row, per_frame;
+    FastDiv div_row, div_frame;  // by per_row and by per_frame
+};
+struct PadSet {
+    PadPlane pl[kMaxPlanes];
+    int n;
+};
+
 // Plane selection over a PlaneSet or a DecodeSet (64- or 32-block batches).
 // Coefficient / var_num pointer of plane k (wave-uniform or not: a select chain, no
 // indexed kernel-argument loads).
@@ -387,6 +411,11 @@ hipError_t launch_block_offsets(const void *lengths, int length_bytes, long long
 // RGB <-> Y/Cb/Cr planes (color.hip); pixel_step 1, 3 or 4
 hipError_t launch_rgb_to_ycc(const ColorArgs &a, int pixel_step, bool s420, hipStream_t stream, int num_cus);
 hipError_t launch_ycc_to_rgb(const ColorArgs &a, int pixel_step, bool s420, hipStream_t stream, int num_cus);
+// the same for a picture of any size and alignment, edge-padded on the way in and cropped on the
+// way out, and the edge padding of plain planes (color_pad.hip)
+hipError_t launch_rgb_to_ycc_pad(const ColorPadArgs &a, int pixel_step, bool s420, hipStream_t stream, int num_cus);
+hipError_t launch_ycc_to_rgb_crop(const ColorPadArgs &a, int pixel_step, bool s420, hipStream_t stream, int num_cus);
+hipError_t launch_pad_planes(const PadSet &s, hipStream_t stream, int num_cus);
 // diagnostic library (fdct8_diag.hip): the lane-per-block fp64 kernels (variant 1)
 hipError_t launch_fdct8_float(const PlaneArgs &p, const DevTables *dev, float *coef, hipStream_t stream);
 hipError_t launch_idct8(const DevTables *dev, int adaptive, const int16_t *coef, const int32_t *var_num,

@@ -352,6 +352,16 @@ int dctq_decode_bits_planes(const dctq_plan *plan, const uint8_t *bytes, const u
  *   header_bytes or nblocks inconsistent with the plane records; a section that
  *   ends past total_bytes; a lengths sum that differs from payload_bytes.
  *
+ * Cropped pictures, format "frame c1": magic "DCTQFRC1", identical to frame v1 in every
+ * byte and rule but one: a plane record's fourth word is pad_right | pad_bottom << 16, the
+ * columns and rows of that stored plane to drop after decoding (the edge padding of
+ * dctq_rgb_to_ycbcr_pad_planes / dctq_pad_planes).  width, height and nblocks stay the
+ * stored, padded ones, and the decode path is frame v1's.  Plain planes: each pad is 0..7.
+ * colour: plane 0 carries 0..15 (4:2:0) or 0..7 (4:4:4), planes 1 and 2 carry 0.  pad_right <
+ * width and pad_bottom < height.  At least one fourth word is non-zero: a picture that needs
+ * no crop is written as frame v1, so every picture has one encoding.  A reader refuses
+ * anything else before it decodes; frame v1 readers go on refusing a non-zero fourth word.
+ *
  * dctq_block_lengths: lengths[b] = min(offsets[b+1] - offsets[b] (mod 2^32),
  * 255 or 65535), nblocks entries of length_bytes (1 or 2) bytes each; nothing
  * past the last entry is written.  max_length[0] = the largest unsaturated
@@ -461,6 +471,39 @@ int dctq_rgb_to_ycbcr_planes(const dctq_rgb *src, const dctq_plane *y, const dct
                              const dctq_plane *cr, void *stream);
 int dctq_ycbcr_to_rgb_planes(const dctq_plane *y, const dctq_plane *cb, const dctq_plane *cr,
                              const dctq_rgb *dst, void *stream);
+
+/* Pictures of any size: edge-pad on the way in, crop on the way out (tools/color_ref.py
+ * pad_edge / forward_padded / inverse_cropped).  With m = 8 in 4:4:4 and m = 16 in 4:2:0, a
+ * picture of W x H (both >= 1) is extended to W' = ceil(W / m) m by H' = ceil(H / m) m,
+ *   pixel'(x, y) = pixel(min(x, W - 1), min(y, H - 1)),
+ * and the transform and the 2x2 chroma averaging above apply to the extended picture
+ * unchanged.  On the way back the inverse above runs on the W' x H' planes and only the
+ * pixels with x < W and y < H are written.
+ * The dctq_rgb carries the true width and height; y must be exactly W' x H', cb and cr equal
+ * to it (4:4:4) or exactly half of it (4:2:0); nframes agree everywhere; the planes obey the
+ * rules of every dctq_plane.  The RGB stack needs NO alignment: any address, any stride >=
+ * width * pixel_step, any frame_stride that covers a frame; pixel_step 1, 3 or 4; channel_stride
+ * +1 or -1 (interleaved) or, planar, any distance of at least one row, either sign.  Anything
+ * else is DCTQ_EINVAL before any launch, and nothing is written.
+ * Writes: the planes over their whole W' x H' and nowhere else; an RGB destination at exactly
+ * the bytes of its W x H pixels (the fourth byte of a 4-byte pixel is written 255) -- row
+ * padding, the bytes between W * pixel_step and stride, and the gaps between frames and
+ * channels stay untouched.  Reads: only bytes of the source's W x H pixels (of a 4-byte pixel
+ * also its fourth byte) -- no byte beside them, aligned or not; the planes are read only
+ * inside W' x H'.  A picture that needs neither padding nor unaligned access gives the bytes
+ * the aligned entry points give.  One launch each, asynchronous on stream; allocate nothing. */
+int dctq_rgb_to_ycbcr_pad_planes(const dctq_rgb *src, const dctq_plane *y, const dctq_plane *cb,
+                                 const dctq_plane *cr, void *stream);
+int dctq_ycbcr_to_rgb_crop_planes(const dctq_plane *y, const dctq_plane *cb, const dctq_plane *cr,
+                                  const dctq_rgb *dst, void *stream);
+/* The same edge replication for 1..4 plain u8 planes in ONE launch: src[k] is any width x
+ * height x nframes (all >= 1) with stride >= width and no alignment rule (its `multiples of
+ * 8` do not apply); dst[k] is a dctq_plane of ceil(width / 8) 8 x ceil(height / 8) 8 and the
+ * same nframes, written over its whole size: dst(x, y) = src(min(x, width - 1), min(y,
+ * height - 1)).  A src that is already whole blocks is copied.  Reads only bytes of src's
+ * width x height.  DCTQ_EINVAL: a NULL pointer, nplanes outside 1..4, a dst of another size, a
+ * dst that starts where a src does (no padding in place). */
+int dctq_pad_planes(const dctq_plane *src, const dctq_plane *dst, int nplanes, void *stream);
 
 /* The calling thread forgets `stream` (call it before hipStreamDestroy): the
  * library keeps no per-stream device memory, only each thread's list of the

@@ -6,6 +6,15 @@ definition and the tests' yardstick: the kernels are held to it byte for byte.
 
     forward(rgb, "420" | "444") -> (y, cb, cr)     rgb u8 [..., H, W, 3]
     inverse(y, cb, cr)          -> rgb             subsampling read from the shapes
+
+Pictures of any size (dctq_rgb_to_ycbcr_pad_planes / dctq_ycbcr_to_rgb_crop_planes): with m = 8
+("444") or 16 ("420") the picture is extended to the next multiples of m by edge replication,
+pixel'(x, y) = pixel(min(x, W - 1), min(y, H - 1)); forward runs on the extended picture; the way
+back runs inverse on the extended planes and keeps the pixels with x < W and y < H.
+
+    pad_edge(a, m)                       -> a, its axes -3 and -2 (H, W of [..., H, W, C]) extended
+    forward_padded(rgb, "420" | "444")   -> forward(pad_edge(rgb, m))
+    inverse_cropped(y, cb, cr, H, W)     -> inverse(y, cb, cr)[..., :H, :W, :]
 """
 import numpy as np
 
@@ -53,6 +62,29 @@ def inverse(y, cb, cr):
         assert cb.shape == cr.shape == y.shape[:-2] + (y.shape[-2] // 2, y.shape[-1] // 2)
         cb, cr = (c.repeat(2, axis=-2).repeat(2, axis=-1) for c in (cb, cr))
     return np.clip(np.stack(rgb_pixels(y, cb, cr), axis=-1), 0, 255).astype(np.uint8)
+
+
+def pad_edge(a, m):
+    """[..., H, W, C] -> [..., ceil(H / m) m, ceil(W / m) m, C] by edge replication, written as the
+    definition's index clamp (not np.pad)."""
+    a = np.asarray(a)
+    h, w = a.shape[-3], a.shape[-2]
+    if h < 1 or w < 1:
+        raise ValueError("a picture needs at least one pixel")
+    ys = np.minimum(np.arange(-(-h // m) * m), h - 1)
+    xs = np.minimum(np.arange(-(-w // m) * m), w - 1)
+    return a[..., ys[:, None], xs[None, :], :]
+
+
+def forward_padded(rgb, subsampling="420"):
+    if subsampling not in ("420", "444"):
+        raise ValueError(subsampling)
+    return forward(pad_edge(rgb, 16 if subsampling == "420" else 8), subsampling)
+
+
+def inverse_cropped(y, cb, cr, H, W):
+    """The inverse over the whole extended planes, then the crop: u8 [..., H, W, 3]."""
+    return np.ascontiguousarray(inverse(y, cb, cr)[..., :H, :W, :])
 
 
 def all_colours():

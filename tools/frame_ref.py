@@ -19,10 +19,17 @@
               payload  payload_bytes bytes of bits v1 (bits_ref.py); total_bytes is its end
   reading   a length above 368 reads as 368; offsets[0] = 0; the sum must be payload_bytes
 
+Cropped pictures, "frame c1": magic b"DCTQFRC1", the same in every byte and rule but one: a plane
+record's fourth word is pad_right | pad_bottom << 16, the columns and rows of that stored (edge-
+padded) plane to drop after decoding.  Plain planes: each pad 0..7.  colour: plane 0 carries 0..15
+(4:2:0) or 0..7 (4:4:4), planes 1 and 2 carry 0.  pad_right < width, pad_bottom < height.  At
+least one word is non-zero: with no crop the container is frame v1, so a picture has one encoding.
+
     pack(payload, offsets, shapes, quality, adaptive=False, var_nums=None, colour=False,
-         length_bytes=None) -> bytes
+         length_bytes=None, crops=None) -> bytes; crops: per plane (pad_bottom, pad_right), or None
     parse(buf) -> dict(quality, adaptive, colour, length_bytes, shapes, nblocks, lengths,
-                       offsets, var_nums, payload); raises FrameError for everything a reader refuses
+                       offsets, var_nums, payload, crops); crops is None for frame v1;
+                       raises FrameError for everything a reader refuses
     lengths_from_offsets(offsets) / offsets_from_lengths(lengths)
     refusal_cases(buf) -> [(rule, bytes)]: a valid container broken once per rule of refusal
 """
@@ -33,6 +40,7 @@ import struct
 import numpy as np
 
 MAGIC = b"DCTQFRM1"
+MAGIC_CROP = b"DCTQFRC1"
 MAX_BLOCK_BYTES = 368       # bits v1: 64 symbols of 46 bits
 MAX_BLOCKS = 11_671_106     # 368 * nblocks < 2^32
 
@@ -84,15 +92,41 @@ def _check_geometry(shapes, colour):
     return n
 
 
-def pack(payload, offsets, shapes, quality, adaptive=False, var_nums=None, colour=False, length_bytes=None) -> bytes:
+def _check_crops(crops, shapes, colour):
+    """The rules of the fourth words of frame c1; crops: per plane (pad_bottom, pad_right)."""
+    if len(crops) != len(shapes):
+        raise FrameError("crops: one (pad_bottom, pad_right) per plane")
+    for k, ((pb, pr), (_, h, w)) in enumerate(zip(crops, shapes)):
+        most = 7
+        if colour:
+            most = 0 if k else (15 if shapes[1][1:] != shapes[0][1:] else 7)
+        if not (0 <= pb <= most and 0 <= pr <= most):
+            raise FrameError(f"plane {k}: pads ({pb}, {pr}) outside 0..{most}")
+        if pr >= w or pb >= h:
+            raise FrameError(f"plane {k}: a pad is not smaller than the plane")
+    if not any(pb or pr for pb, pr in crops):
+        raise FrameError("frame c1 with no crop: that picture is frame v1")
+
+
+def pack(payload, offsets, shapes, quality, adaptive=False, var_nums=None, colour=False, length_bytes=None,
+         crops=None) -> bytes:
     """payload: the bits v1 bytes; offsets: its N + 1 byte offsets; shapes: per plane (F, H, W) or
     (H, W); var_nums: int32 [N] (or per-plane pieces), needed when adaptive.  length_bytes None:
-    1 when every block is at most 255 B, else 2."""
+    1 when every block is at most 255 B, else 2.  crops: per plane (pad_bottom, pad_right); None or
+    all zero gives frame v1, anything else frame c1."""
     shapes = _shapes3(shapes)
+    if crops is not None:
+        crops = [tuple(map(int, c)) for c in crops]
+        if len(crops) != len(shapes):
+            raise FrameError("crops: one (pad_bottom, pad_right) per plane")
+        if not any(pb or pr for pb, pr in crops):
+            crops = None
     quality = int(quality)
     if not 1 <= quality <= 100:
         raise FrameError("quality must be 1..100")
     nblocks = _check_geometry(shapes, colour)
+    if crops is not None:
+        _check_crops(crops, shapes, colour)
     payload = bytes(np.ascontiguousarray(payload, np.uint8)) if not isinstance(payload, (bytes, bytearray)) else bytes(payload)
     off = np.asarray(offsets).astype(np.int64) & 0xFFFFFFFF
     if off.shape != (nblocks + 1,) or off[0] != 0 or off[-1] != len(payload):
@@ -118,11 +152,11 @@ def pack(payload, offsets, shapes, quality, adaptive=False, var_nums=None, colou
     total = header_bytes
     for s in sections:
         total = align16(total) + len(s)
-    out = bytearray(MAGIC)
+    out = bytearray(MAGIC if crops is None else MAGIC_CROP)
     out += struct.pack("<IBBBBB7xQQQ", header_bytes, quality, int(bool(adaptive)), len(shapes), length_bytes,
                        int(bool(colour)), nblocks, len(payload), total)
-    for f, h, w in shapes:
-        out += struct.pack("<IIII", w, h, f, 0)
+    for (f, h, w), (pb, pr) in zip(shapes, crops or [(0, 0)] * len(shapes)):
+        out += struct.pack("<IIII", w, h, f, pr | pb << 16)
     assert len(out) == header_bytes
     for s in sections:
         out += bytes(align16(len(out)) - len(out)) + s
@@ -135,8 +169,9 @@ def parse(buf) -> dict:
     buf = bytes(np.ascontiguousarray(buf, np.uint8)) if not isinstance(buf, (bytes, bytearray)) else bytes(buf)
     if len(buf) < 48:
         raise FrameError("shorter than the fixed header")
-    if buf[:8] != MAGIC:
+    if buf[:8] not in (MAGIC, MAGIC_CROP):
         raise FrameError("bad magic")
+    cropped = buf[:8] == MAGIC_CROP
     header_bytes, quality, adaptive, nplanes, length_bytes, colour = struct.unpack_from("<IBBBBB", buf, 8)
     nblocks, payload_bytes, total = struct.unpack_from("<QQQ", buf, 24)
     if not 1 <= quality <= 100 or adaptive > 1 or not 1 <= nplanes <= 4 or length_bytes not in (1, 2) or colour > 1:
@@ -147,14 +182,19 @@ def parse(buf) -> dict:
         raise FrameError("header_bytes does not match nplanes")
     if len(buf) < header_bytes:
         raise FrameError("shorter than header_bytes")
-    shapes = []
+    shapes, words = [], []
     for k in range(nplanes):
-        w, h, f, zero = struct.unpack_from("<IIII", buf, 48 + 16 * k)
-        if zero:
+        w, h, f, word = struct.unpack_from("<IIII", buf, 48 + 16 * k)
+        if word and not cropped:
             raise FrameError("a plane record's fourth word is not 0")
         shapes.append((f, h, w))
+        words.append(word)
     if _check_geometry(shapes, colour) != nblocks:
         raise FrameError("nblocks does not match the plane records")
+    crops = None
+    if cropped:
+        crops = [(word >> 16, word & 0xFFFF) for word in words]
+        _check_crops(crops, shapes, colour)
     if payload_bytes >= 1 << 32:
         raise FrameError("payload_bytes must stay below 2^32")
     if len(buf) < total:
@@ -176,11 +216,12 @@ def parse(buf) -> dict:
     var_nums = np.frombuffer(buf, "<i4", nblocks, starts[1]).astype(np.int32) if adaptive else None
     return {"quality": quality, "adaptive": bool(adaptive), "colour": bool(colour), "length_bytes": length_bytes,
             "shapes": shapes, "nblocks": nblocks, "lengths": lengths.copy(), "offsets": offsets, "var_nums": var_nums,
-            "payload": buf[starts[-1]:starts[-1] + payload_bytes]}
+            "payload": buf[starts[-1]:starts[-1] + payload_bytes], "crops": crops}
 
 
 def refusal_cases(buf):
-    """[(rule, bytes)]: one mutation of the valid container `buf` per rule a reader refuses by."""
+    """[(rule, bytes)]: one mutation of the valid container `buf` per rule a reader refuses by.  A
+    frame c1 buffer gets the rules of its fourth words instead of "fourth word set"."""
     buf = bytes(buf)
     header_bytes, = struct.unpack_from("<I", buf, 8)
     nblocks, payload_bytes, total = struct.unpack_from("<QQQ", buf, 24)
@@ -191,7 +232,7 @@ def refusal_cases(buf):
         return bytes(b)
 
     first_length = align16(header_bytes)
-    return [
+    cases = [
         ("shorter than 48 bytes", buf[:47]),
         ("shorter than header_bytes", buf[:header_bytes - 1]),
         ("shorter than total_bytes", buf[:total - 1]),
@@ -213,3 +254,26 @@ def refusal_cases(buf):
         ("a section ends past total_bytes", put("<Q", 40, total - 1)),
         ("lengths sum differs", put("<B", first_length, buf[first_length] + 1 & 0xFF)),
     ]
+    if buf[:8] != MAGIC_CROP:
+        return cases
+    nplanes, colour = buf[14], buf[16]
+    (w0, h0), (w1, h1) = (struct.unpack_from("<II", buf, 48 + 16 * min(k, nplanes - 1)) for k in (0, 1))
+    most = (15 if (w1, h1) != (w0, h0) else 7) if colour else 7
+    word0, = struct.unpack_from("<I", buf, 60)
+    zeroed = bytearray(buf)
+    for k in range(nplanes):
+        struct.pack_into("<I", zeroed, 60 + 16 * k, 0)
+    cases = [c for c in cases if c[0] != "plane record's fourth word set"]
+    cases[3] = ("bad magic", b"DCTQFRC2" + buf[8:])
+    cases += [
+        ("pad_right above the most", put("<I", 60, (word0 & 0xFFFF0000) | (most + 1))),
+        ("pad_bottom above the most", put("<I", 60, (word0 & 0xFFFF) | (most + 1) << 16)),
+        ("pad_right with high bits", put("<I", 60, word0 | 0x8000)),
+        ("pad_bottom with high bits", put("<I", 60, word0 | 0x80000000)),
+        ("no crop at all under the crop magic", bytes(zeroed)),
+        ("the fourth words under the frame v1 magic", MAGIC + buf[8:]),
+    ]
+    if colour:
+        cases += [("a chroma plane with a pad", put("<I", 60 + 16, 1)),
+                  ("a chroma plane with a bottom pad", put("<I", 60 + 32, 1 << 16))]
+    return cases
