@@ -241,6 +241,9 @@ int dctq_rle_count(const int16_t *coef, long long nblocks, uint32_t *offsets, vo
 int dctq_rle_emit(const int16_t *coef, long long nblocks, const uint32_t *offsets, uint32_t *symbols, void *stream);
 /* The inverse, run_length_decode (src/entropy.c:327-351) + zigzag_to_block
  * (:183-210) of every block: coef[b][64] from symbols[offsets[b] ..).
+ * By that rule (pos += run; the value lands while pos < 64; pos++) a block
+ * with no symbols decodes to zeros, and symbols after position 63 is passed,
+ * or beyond a block's 64th, change nothing -- any symbols are a valid input.
  * dctq_rle_decode16: the same from 2-byte symbols ((run & 63) << 10 | (value &
  * 0x3FF), 0x0000 = (0, 64); dctq_encode_planes16's output);
  * symbols 4-byte aligned. */
