@@ -25,12 +25,34 @@ int fail(int code, const char *what, hipError_t e) {
 }  // namespace dctq
 using dctq::fail;
 
+// The small checks that several entry points share, each with its one wording.
+static bool misaligned(const void *p, uintptr_t n) { return ((uintptr_t)p) % n != 0; }
+
+static int check_workspace(const void *workspace) {
+    if (!workspace) return fail(DCTQ_EINVAL, "workspace is NULL");
+    if (misaligned(workspace, 4)) return fail(DCTQ_EINVAL, "workspace must be 4-byte aligned");
+    return DCTQ_OK;
+}
+
+static int check_nplanes(int nplanes) {
+    if (nplanes < 1 || nplanes > dctq::kMaxPlanes) return fail(DCTQ_EINVAL, "nplanes must be in [1, 4]");
+    return DCTQ_OK;
+}
+
+static int check_symbol_bytes(int symbol_bytes) {
+    if (symbol_bytes != 2 && symbol_bytes != 4) return fail(DCTQ_EINVAL, "symbol_bytes must be 2 or 4");
+    return DCTQ_OK;
+}
+
+// what the three *_workspace_bytes exports of the offset scans answer: a count below 1 asks for one block's
+static size_t scan_workspace_bytes(long long nblocks) { return dctq::rle_workspace_bytes(nblocks < 1 ? 1 : nblocks); }
+
 int dctq::plane_args(const dctq_plane *s, dctq::PlaneArgs *a) {
     if (!s || !s->pixels) return fail(DCTQ_EINVAL, "plane/pixels is NULL");
     if (s->width <= 0 || s->height <= 0 || s->width % 8 || s->height % 8)
         return fail(DCTQ_EINVAL, "width and height must be positive multiples of 8");
     if (s->stride < s->width || s->stride % 8) return fail(DCTQ_EINVAL, "stride must be >= width and a multiple of 8");
-    if (((uintptr_t)s->pixels) % 8 || s->frame_stride % 8) return fail(DCTQ_EINVAL, "pixels/frame_stride must be 8-byte aligned");
+    if (misaligned(s->pixels, 8) || s->frame_stride % 8) return fail(DCTQ_EINVAL, "pixels/frame_stride must be 8-byte aligned");
     if (s->nframes < 1) return fail(DCTQ_EINVAL, "nframes must be >= 1");
     if (s->nframes > 1 && s->frame_stride < s->stride * (long long)s->height)
         return fail(DCTQ_EINVAL, "frame_stride smaller than one frame");
@@ -87,7 +109,7 @@ static int number_blocks(dctq::EncodeSet *es, long long limit, const char *too_m
 
 int dctq::plane_inputs(const dctq_plane *planes, int nplanes, dctq::PlaneSet *ps_out) {
     if (!planes) return fail(DCTQ_EINVAL, "planes is NULL");
-    if (nplanes < 1 || nplanes > dctq::kMaxPlanes) return fail(DCTQ_EINVAL, "nplanes must be in [1, 4]");
+    if (int rc = check_nplanes(nplanes)) return rc;
     dctq::PlaneSet &ps = *ps_out;
     ps = {};
     ps.n = nplanes;
@@ -104,7 +126,7 @@ int dctq::plane_set(const dctq_plane *planes, int nplanes, int16_t *const *coef,
     dctq::PlaneSet &ps = *ps_out;
     for (int k = 0; k < nplanes; ++k) {
         if (!coef[k]) return fail(DCTQ_EINVAL, "coef[k] is NULL");
-        if (((uintptr_t)coef[k]) % 16) return fail(DCTQ_EINVAL, "coef must be 16-byte aligned");
+        if (misaligned(coef[k], 16)) return fail(DCTQ_EINVAL, "coef must be 16-byte aligned");
         if (var_num && !var_num[k]) return fail(DCTQ_EINVAL, "var_num given but var_num[k] is NULL");
         ps.coef[k] = coef[k];
         ps.var[k] = var_num ? var_num[k] : nullptr;
@@ -136,7 +158,7 @@ int dctq_round_trip_planes(const dctq_plan *plan, const dctq_plane *planes, int 
     int rc = dctq::plane_set(planes, nplanes, coef, var_num, &rt.ps);
     if (rc) return rc;
     for (int k = 0; k < nplanes; ++k) {
-        if (!recon[k] || ((uintptr_t)recon[k]) % 16) return fail(DCTQ_EINVAL, "recon[k] NULL or not 16-byte aligned");
+        if (!recon[k] || misaligned(recon[k], 16)) return fail(DCTQ_EINVAL, "recon[k] NULL or not 16-byte aligned");
         rt.recon[k] = recon[k];
     }
     HIPCHK(dctq::launch_roundtrip(rt, plan->dev, plan->adaptive, plan->inv_f32 != 0, plan->fallbacks,
@@ -159,8 +181,8 @@ static int encode_planes(const dctq_plan *plan, const dctq_plane *planes, int np
     if (int rc = dctq::check_plan(plan)) return rc;
     if (!offsets || !workspace) return fail(DCTQ_EINVAL, "offsets/workspace is NULL");
     if (symbols_capacity < 0) return fail(DCTQ_EINVAL, "symbols_capacity < 0");
-    if (((uintptr_t)symbols) % 4) return fail(DCTQ_EINVAL, "symbols must be 4-byte aligned");
-    if (((uintptr_t)workspace) % 4) return fail(DCTQ_EINVAL, "workspace must be 4-byte aligned");
+    if (misaligned(symbols, 4)) return fail(DCTQ_EINVAL, "symbols must be 4-byte aligned");
+    if (int rc = check_workspace(workspace)) return rc;
     if (symbol_bytes == 2 && plan->symbol_bytes != 2)
         return fail(DCTQ_EINVAL, "the plan's quantized coefficients can exceed 511: 2-byte symbols cannot hold them "
                                  "(dctq_plan_symbol_bytes == 4; use dctq_encode_planes)");
@@ -198,7 +220,7 @@ int dctq_forward_float(const dctq_plan *plan, const dctq_plane *src, float *coef
     DCTQ_LAUNCH(stream, dctq::kEntryForwardFloat);
     if (int rc = dctq::check_plan(plan)) return rc;
     if (!coef) return fail(DCTQ_EINVAL, "coef is NULL");
-    if (((uintptr_t)coef) % 16) return fail(DCTQ_EINVAL, "coef must be 16-byte aligned");
+    if (misaligned(coef, 16)) return fail(DCTQ_EINVAL, "coef must be 16-byte aligned");
     dctq::PlaneArgs a;
     int rc = dctq::plane_args(src, &a);
     if (rc) return rc;
@@ -214,7 +236,7 @@ int dctq_inverse(const dctq_plan *plan, const int16_t *coef, const int32_t *var_
     if (!coef || !recon) return fail(DCTQ_EINVAL, "coef/recon is NULL");
     if (plan->adaptive && !var_num) return fail(DCTQ_EINVAL, "adaptive inverse needs var_num");
     if (nblocks < 0 || nblocks >= (1ll << 40)) return fail(DCTQ_EINVAL, "bad nblocks");
-    if (((uintptr_t)coef) % 16 || ((uintptr_t)recon) % 16) return fail(DCTQ_EINVAL, "coef/recon must be 16-byte aligned");
+    if (misaligned(coef, 16) || misaligned(recon, 16)) return fail(DCTQ_EINVAL, "coef/recon must be 16-byte aligned");
     if (nblocks == 0) return DCTQ_OK;
     HIPCHK(dctq::launch_idct8_pair(plan->dev, plan->adaptive, coef, var_num, nblocks, recon, (hipStream_t)stream,
                                    plan->num_cus),
@@ -227,7 +249,7 @@ int dctq_inverse(const dctq_plan *plan, const int16_t *coef, const int32_t *var_
 extern "C++" template <typename F>
 static int decoder_planes(const dctq_plan *plan, const int32_t *const *var_num, const dctq_plane *dst, int nplanes,
                           dctq::PlaneArgs *pl, const int32_t **var, F &&input) {
-    if (nplanes < 1 || nplanes > dctq::kMaxPlanes) return fail(DCTQ_EINVAL, "nplanes must be in [1, 4]");
+    if (int rc = check_nplanes(nplanes)) return rc;
     if (plan->adaptive && !var_num) return fail(DCTQ_EINVAL, "adaptive decode needs var_num");
     for (int k = 0; k < nplanes; ++k) {
         if (int rc = dctq::plane_args(&dst[k], &pl[k])) return rc;
@@ -247,7 +269,7 @@ int dctq_decode_planes(const dctq_plan *plan, const int16_t *const *coef, const 
     ds.n = nplanes;
     const auto coef_of_plane = [&](int k) {
         if (!coef[k]) return fail(DCTQ_EINVAL, "coef[k] is NULL");
-        if (((uintptr_t)coef[k]) % 16) return fail(DCTQ_EINVAL, "coef must be 16-byte aligned");
+        if (misaligned(coef[k], 16)) return fail(DCTQ_EINVAL, "coef must be 16-byte aligned");
         ds.coef[k] = coef[k];
         return (int)DCTQ_OK;
     };
@@ -276,8 +298,8 @@ int dctq_decode_symbols_planes(const dctq_plan *plan, const void *symbols, int s
     DCTQ_LAUNCH(stream, dctq::kEntryDecodeSymbolsPlanes);
     if (int rc = dctq::check_plan(plan)) return rc;
     if (!symbols || !offsets || !dst) return fail(DCTQ_EINVAL, "symbols/offsets/dst is NULL");
-    if (symbol_bytes != 2 && symbol_bytes != 4) return fail(DCTQ_EINVAL, "symbol_bytes must be 2 or 4");
-    if (((uintptr_t)symbols) % 4 || ((uintptr_t)offsets) % 4) return fail(DCTQ_EINVAL, "symbols/offsets must be 4-byte aligned");
+    if (int rc = check_symbol_bytes(symbol_bytes)) return rc;
+    if (misaligned(symbols, 4) || misaligned(offsets, 4)) return fail(DCTQ_EINVAL, "symbols/offsets must be 4-byte aligned");
     dctq::SymbolSet ss;
     if (int rc = symbol_set(plan, var_num, dst, nplanes, &ss)) return rc;
     HIPCHK(dctq::launch_decode_symbols(ss, symbols, symbol_bytes, offsets, plan->dev, plan->adaptive,
@@ -291,7 +313,7 @@ int dctq_decode_bits_planes(const dctq_plan *plan, const uint8_t *bytes, const u
     DCTQ_LAUNCH(stream, dctq::kEntryDecodeBitsPlanes);
     if (int rc = dctq::check_plan(plan)) return rc;
     if (!bytes || !offsets || !dst) return fail(DCTQ_EINVAL, "bytes/offsets/dst is NULL");
-    if (((uintptr_t)offsets) % 4) return fail(DCTQ_EINVAL, "offsets must be 4-byte aligned");
+    if (misaligned(offsets, 4)) return fail(DCTQ_EINVAL, "offsets must be 4-byte aligned");
     dctq::SymbolSet ss;
     if (int rc = symbol_set(plan, var_num, dst, nplanes, &ss)) return rc;
     HIPCHK(dctq::launch_decode_bits(ss, bytes, offsets, plan->dev, plan->adaptive, plan->inv_f32 != 0,
@@ -304,7 +326,7 @@ int dctq_synth(uint64_t seed, int kind, const dctq_plane *dst, void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntrySynth);
     if (!dst || !dst->pixels) return fail(DCTQ_EINVAL, "dst is NULL");
     if (dst->width <= 0 || dst->height <= 0 || dst->width % 4 || dst->stride < dst->width || dst->stride % 4 ||
-        dst->nframes < 1 || ((uintptr_t)dst->pixels) % 4)
+        dst->nframes < 1 || misaligned(dst->pixels, 4))
         return fail(DCTQ_EINVAL, "bad synth plane geometry");
     HIPCHK(dctq::launch_synth(seed, kind, (uint8_t *)dst->pixels, dst->stride, dst->frame_stride, dst->width,
                               dst->height, dst->nframes, (hipStream_t)stream),
@@ -325,13 +347,12 @@ static int rle_args(const void *a, const void *b, long long nblocks) {
     return DCTQ_OK;
 }
 
-size_t dctq_rle_workspace_bytes(long long nblocks) { return dctq::rle_workspace_bytes(nblocks < 1 ? 1 : nblocks); }
+size_t dctq_rle_workspace_bytes(long long nblocks) { return scan_workspace_bytes(nblocks); }
 
 int dctq_rle_count(const int16_t *coef, long long nblocks, uint32_t *offsets, void *workspace, void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntryRleCount);
     if (int rc = rle_args(coef, offsets, nblocks)) return rc;
-    if (!workspace) return fail(DCTQ_EINVAL, "workspace is NULL");
-    if (((uintptr_t)workspace) % 4) return fail(DCTQ_EINVAL, "workspace must be 4-byte aligned");
+    if (int rc = check_workspace(workspace)) return rc;
     HIPCHK(dctq::launch_rle_count(coef, nblocks, offsets, workspace, (hipStream_t)stream, device_cus()),
            "rle_count launch");
     return DCTQ_OK;
@@ -361,26 +382,26 @@ int dctq_rle_decode16(const uint16_t *symbols, const uint32_t *offsets, long lon
     DCTQ_LAUNCH(stream, dctq::kEntryRleDecode16);
     if (int rc = rle_args(symbols, offsets, nblocks)) return rc;
     if (!coef) return fail(DCTQ_EINVAL, "coef is NULL");
-    if (((uintptr_t)symbols) % 4) return fail(DCTQ_EINVAL, "symbols must be 4-byte aligned");
+    if (misaligned(symbols, 4)) return fail(DCTQ_EINVAL, "symbols must be 4-byte aligned");
     HIPCHK(dctq::launch_rle_decode(symbols, 2, offsets, nblocks, coef, (hipStream_t)stream, device_cus()),
            "rle_decode16 launch");
     return DCTQ_OK;
 }
 
-size_t dctq_bits_workspace_bytes(long long nblocks) { return dctq::rle_workspace_bytes(nblocks < 1 ? 1 : nblocks); }
+size_t dctq_bits_workspace_bytes(long long nblocks) { return scan_workspace_bytes(nblocks); }
 
 int dctq_bits_pack(const void *symbols, int symbol_bytes, const uint32_t *sym_offsets, long long nblocks,
                    uint32_t *offsets, uint8_t *bytes, long long bytes_capacity, void *workspace, void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntryBitsPack);
     if (int rc = rle_args(symbols, sym_offsets, nblocks)) return rc;
     if (!offsets || !workspace) return fail(DCTQ_EINVAL, "offsets/workspace is NULL");
-    if (symbol_bytes != 2 && symbol_bytes != 4) return fail(DCTQ_EINVAL, "symbol_bytes must be 2 or 4");
+    if (int rc = check_symbol_bytes(symbol_bytes)) return rc;
     // offsets are 32-bit and a block takes up to 368 B
     if (368 * nblocks >= (1ll << 32)) return fail(DCTQ_EINVAL, "368 * nblocks must stay below 2^32");
     if (bytes_capacity < 0) return fail(DCTQ_EINVAL, "bytes_capacity < 0");
-    if (((uintptr_t)symbols) % 4 || ((uintptr_t)sym_offsets) % 4 || ((uintptr_t)offsets) % 4 || ((uintptr_t)bytes) % 4)
+    if (misaligned(symbols, 4) || misaligned(sym_offsets, 4) || misaligned(offsets, 4) || misaligned(bytes, 4))
         return fail(DCTQ_EINVAL, "symbols/sym_offsets/offsets/bytes must be 4-byte aligned");
-    if (((uintptr_t)workspace) % 4) return fail(DCTQ_EINVAL, "workspace must be 4-byte aligned");
+    if (int rc = check_workspace(workspace)) return rc;
     HIPCHK(dctq::launch_bits_pack(symbols, symbol_bytes, sym_offsets, nblocks, offsets, bytes,
                                   bytes ? (unsigned long long)bytes_capacity : 0ull, workspace, (hipStream_t)stream,
                                   device_cus()),
@@ -392,7 +413,7 @@ int dctq_bits_decode(const uint8_t *bytes, const uint32_t *offsets, long long nb
     DCTQ_LAUNCH(stream, dctq::kEntryBitsDecode);
     if (int rc = rle_args(bytes, offsets, nblocks)) return rc;
     if (!coef) return fail(DCTQ_EINVAL, "coef is NULL");
-    if (((uintptr_t)offsets) % 4 || ((uintptr_t)coef) % 16) return fail(DCTQ_EINVAL, "offsets must be 4-byte, coef 16-byte aligned");
+    if (misaligned(offsets, 4) || misaligned(coef, 16)) return fail(DCTQ_EINVAL, "offsets must be 4-byte, coef 16-byte aligned");
     HIPCHK(dctq::launch_bits_decode(bytes, offsets, nblocks, coef, (hipStream_t)stream, device_cus()),
            "bits_decode launch");
     return DCTQ_OK;
@@ -403,7 +424,7 @@ static int frame_args(const void *offsets, const void *lengths, int length_bytes
     if (!offsets || !lengths) return fail(DCTQ_EINVAL, "offsets/lengths is NULL");
     if (length_bytes != 1 && length_bytes != 2) return fail(DCTQ_EINVAL, "length_bytes must be 1 or 2");
     if (nblocks < 1 || 368 * nblocks >= (1ll << 32)) return fail(DCTQ_EINVAL, "nblocks must be in [1, 11671106]");
-    if (((uintptr_t)offsets) % 4 || ((uintptr_t)lengths) % 4)
+    if (misaligned(offsets, 4) || misaligned(lengths, 4))
         return fail(DCTQ_EINVAL, "offsets and lengths must be 4-byte aligned");
     return DCTQ_OK;
 }
@@ -412,23 +433,20 @@ int dctq_block_lengths(const uint32_t *offsets, long long nblocks, int length_by
                        uint32_t *max_length, void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntryBlockLengths);
     if (int rc = frame_args(offsets, lengths, length_bytes, nblocks)) return rc;
-    if (!max_length || ((uintptr_t)max_length) % 4) return fail(DCTQ_EINVAL, "max_length is NULL or not 4-byte aligned");
+    if (!max_length || misaligned(max_length, 4)) return fail(DCTQ_EINVAL, "max_length is NULL or not 4-byte aligned");
     HIPCHK(dctq::launch_block_lengths(offsets, nblocks, length_bytes, lengths, max_length, (hipStream_t)stream,
                                       device_cus()),
            "block_lengths launch");
     return DCTQ_OK;
 }
 
-size_t dctq_block_offsets_workspace_bytes(long long nblocks) {
-    return dctq::rle_workspace_bytes(nblocks < 1 ? 1 : nblocks);
-}
+size_t dctq_block_offsets_workspace_bytes(long long nblocks) { return scan_workspace_bytes(nblocks); }
 
 int dctq_block_offsets(const void *lengths, int length_bytes, long long nblocks, uint32_t *offsets, void *workspace,
                        void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntryBlockOffsets);
     if (int rc = frame_args(offsets, lengths, length_bytes, nblocks)) return rc;
-    if (!workspace) return fail(DCTQ_EINVAL, "workspace is NULL");
-    if (((uintptr_t)workspace) % 4) return fail(DCTQ_EINVAL, "workspace must be 4-byte aligned");
+    if (int rc = check_workspace(workspace)) return rc;
     HIPCHK(dctq::launch_block_offsets(lengths, length_bytes, nblocks, offsets, workspace, (hipStream_t)stream,
                                       device_cus()),
            "block_offsets launch");
@@ -439,7 +457,7 @@ int dctq_huffman_bits(const int16_t *coef, long long nblocks, uint32_t *bits, vo
     DCTQ_LAUNCH(stream, dctq::kEntryHuffmanBits);
     if (!coef || !bits) return fail(DCTQ_EINVAL, "coef/bits is NULL");
     if (nblocks < 0) return fail(DCTQ_EINVAL, "nblocks < 0");
-    if (((uintptr_t)coef) % 16 || ((uintptr_t)bits) % 4) return fail(DCTQ_EINVAL, "coef must be 16-byte, bits 4-byte aligned");
+    if (misaligned(coef, 16) || misaligned(bits, 4)) return fail(DCTQ_EINVAL, "coef must be 16-byte, bits 4-byte aligned");
     if (nblocks == 0) return DCTQ_OK;
     HIPCHK(dctq::launch_huffman_bits(coef, nblocks, bits, (hipStream_t)stream, device_cus()), "huffman_bits launch");
     return DCTQ_OK;
@@ -449,7 +467,7 @@ int dctq_huffman_bits_planes(const dctq_plan *plan, const dctq_plane *planes, in
                              void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntryHuffmanBitsPlanes);
     if (int rc = dctq::check_plan(plan)) return rc;
-    if (!bits || ((uintptr_t)bits) % 4) return fail(DCTQ_EINVAL, "bits is NULL or not 4-byte aligned");
+    if (!bits || misaligned(bits, 4)) return fail(DCTQ_EINVAL, "bits is NULL or not 4-byte aligned");
     // pixel planes only: the coefficients stay on chip (es.ps.coef stays NULL)
     dctq::EncodeSet es = {};
     int rc = dctq::plane_inputs(planes, nplanes, &es.ps);
@@ -464,7 +482,7 @@ int dctq_distortion_planes(const dctq_plan *plan, const dctq_plane *planes, int 
                            void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntryDistortionPlanes);
     if (int rc = dctq::check_plan(plan)) return rc;
-    if (!sse || ((uintptr_t)sse) % 4) return fail(DCTQ_EINVAL, "sse is NULL or not 4-byte aligned");
+    if (!sse || misaligned(sse, 4)) return fail(DCTQ_EINVAL, "sse is NULL or not 4-byte aligned");
     // pixel planes only: no coefficient, var_num or picture buffer (es.ps.coef / var stay NULL)
     dctq::EncodeSet es = {};
     int rc = dctq::plane_inputs(planes, nplanes, &es.ps);
@@ -476,42 +494,80 @@ int dctq_distortion_planes(const dctq_plan *plan, const dctq_plane *planes, int 
     return DCTQ_OK;
 }
 
-// The colour kernels' arguments from an RGB stack and its three planes, everything checked:
-// *pixel_step and *s420 select the kernel.
+// A source stack's own geometry: a stride that covers a row of row_bytes and, for more than one frame, a
+// frame_stride that covers a frame; with `sizes`, width, height and nframes >= 1 first.  `what` names the stack.
+static int stack_geometry(const char *what, bool sizes, int width, int height, int nframes, long long row_bytes,
+                          long long stride, long long frame_stride) {
+    const auto refuse = [&](const char *rule) { return fail(DCTQ_EINVAL, (std::string(what) + rule).c_str()); };
+    if (sizes && (width < 1 || height < 1 || nframes < 1)) return refuse("width, height and nframes must be >= 1");
+    if (stride < row_bytes) return refuse("stride smaller than one row");
+    if (nframes > 1 && frame_stride < stride * (long long)height) return refuse("frame_stride smaller than one frame");
+    return DCTQ_OK;
+}
+
+// The patch grid of ColorArgs or a PadPlane: per_row x rows patches a frame in raster order over nframes frames,
+// fewer than 2^31 of them or the refusal `too_many`.
+extern "C++" template <typename Args>
+static int patch_grid(Args &a, long long per_row, long long rows, long long nframes, const char *too_many) {
+    const long long per_frame = per_row * rows;
+    if (per_frame * nframes >= (1ll << 31)) return fail(DCTQ_EINVAL, too_many);
+    a.npatch = (uint32_t)(per_frame * nframes);
+    a.per_row = (uint32_t)per_row;
+    a.per_frame = (uint32_t)per_frame;
+    a.div_row = dctq::make_fastdiv(a.per_row);
+    a.div_frame = dctq::make_fastdiv(a.per_frame);
+    return DCTQ_OK;
+}
+
+// The colour kernels' arguments from an RGB stack and its three planes, everything checked: *pixel_step and
+// *s420 select the kernel.  The aligned entry points want the stack at dword alignment and of the Y plane's
+// size.  any_size (the padding ones): the stack is the true W x H picture at any alignment, the planes are
+// its extension to whole blocks, and *aligned says that it needs neither padding nor unaligned access, so
+// that out->c describes the same call to the aligned kernels.
 static int color_args(const dctq_rgb *rgb, const dctq_plane *y, const dctq_plane *cb, const dctq_plane *cr,
-                      dctq::ColorArgs *out, int *pixel_step, bool *s420) {
+                      bool any_size, dctq::ColorPadArgs *out, int *pixel_step, bool *s420, bool *aligned) {
     if (!rgb || !rgb->pixels) return fail(DCTQ_EINVAL, "rgb/pixels is NULL");
     const int step = rgb->pixel_step;
     if (step != 1 && step != 3 && step != 4) return fail(DCTQ_EINVAL, "pixel_step must be 1, 3 or 4");
     const long long cs = rgb->channel_stride;
-    if (step == 1 ? (cs == 0 || cs % 4) : (cs != 1 && cs != -1))
-        return fail(DCTQ_EINVAL, "channel_stride must be +1 or -1 (interleaved) or a non-zero multiple of 4 (planar)");
+    const bool planar_dwords = step != 1 || cs % 4 == 0;
+    if (step == 1 ? (cs == 0 || (!any_size && !planar_dwords)) : (cs != 1 && cs != -1))
+        return fail(DCTQ_EINVAL, any_size ? "channel_stride must be +1 or -1 (interleaved) or non-zero (planar)"
+                                          : "channel_stride must be +1 or -1 (interleaved) or a non-zero multiple of 4 "
+                                            "(planar)");
     // the lowest byte of pixel (0,0): its B byte when the order is B, G, R
     uint8_t *first = (uint8_t *)rgb->pixels - (step != 1 && cs == -1 ? 2 : 0);
-    if (((uintptr_t)first) % 4 || rgb->stride % 4 || rgb->frame_stride % 4)
+    const bool dwords = !misaligned(first, 4) && rgb->stride % 4 == 0 && rgb->frame_stride % 4 == 0;
+    if (!any_size && !dwords)
         return fail(DCTQ_EINVAL, "rgb: the lowest byte of pixel (0,0) must be 4-byte aligned, stride and frame_stride "
                                  "multiples of 4");
+    // sizes: only where they are the stack's own; otherwise they are the Y plane's, checked below
+    if (int rc = stack_geometry("rgb: ", any_size, rgb->width, rgb->height, rgb->nframes, (long long)rgb->width * step,
+                                rgb->stride, rgb->frame_stride))
+        return rc;
     dctq::PlaneArgs py, pb, pr;
     if (int rc = dctq::plane_args(y, &py)) return rc;
     if (int rc = dctq::plane_args(cb, &pb)) return rc;
     if (int rc = dctq::plane_args(cr, &pr)) return rc;
-    if (rgb->width != y->width || rgb->height != y->height)
-        return fail(DCTQ_EINVAL, "the RGB stack and the Y plane differ in width or height");
-    if (rgb->nframes != y->nframes || cb->nframes != y->nframes || cr->nframes != y->nframes)
-        return fail(DCTQ_EINVAL, "the RGB stack and the planes differ in nframes");
-    if (rgb->stride < (long long)rgb->width * step) return fail(DCTQ_EINVAL, "rgb: stride smaller than one row");
-    if (rgb->nframes > 1 && rgb->frame_stride < rgb->stride * (long long)rgb->height)
-        return fail(DCTQ_EINVAL, "rgb: frame_stride smaller than one frame");
-    if (step == 1 && (cs < 0 ? -cs : cs) < rgb->width) return fail(DCTQ_EINVAL, "rgb: channel_stride smaller than one row");
     if (cb->width != cr->width || cb->height != cr->height) return fail(DCTQ_EINVAL, "Cb and Cr differ in size");
     const bool full = cb->width == y->width && cb->height == y->height;
     const bool half = 2ll * cb->width == y->width && 2ll * cb->height == y->height;
     if (!full && !half)
         return fail(DCTQ_EINVAL, "chroma must be luma's size (4:4:4) or exactly half of it in both directions (4:2:0)");
-    const long long per_row = y->width / 8, per_frame = per_row * (y->height / (half ? 2 : 1));
-    if (per_frame * y->nframes >= (1ll << 31)) return fail(DCTQ_EINVAL, "2^31 patches or more in one call");
-    dctq::ColorArgs &a = *out;
-    a = {};
+    const bool whole = rgb->width == y->width && rgb->height == y->height;
+    const long long m = half ? 16 : 8;
+    if (!any_size) {
+        if (!whole) return fail(DCTQ_EINVAL, "the RGB stack and the Y plane differ in width or height");
+    } else if (y->width != (rgb->width + m - 1) / m * m || y->height != (rgb->height + m - 1) / m * m) {
+        return fail(DCTQ_EINVAL, "the Y plane is not the RGB stack's size rounded up to whole blocks (8, or 16 in 4:2:0)");
+    }
+    if (rgb->nframes != y->nframes || cb->nframes != y->nframes || cr->nframes != y->nframes)
+        return fail(DCTQ_EINVAL, "the RGB stack and the planes differ in nframes");
+    if (step == 1 && (cs < 0 ? -cs : cs) < rgb->width) return fail(DCTQ_EINVAL, "rgb: channel_stride smaller than one row");
+    *out = {};
+    dctq::ColorArgs &a = out->c;
+    if (int rc = patch_grid(a, y->width / 8, y->height / (half ? 2 : 1), y->nframes, "2^31 patches or more in one call"))
+        return rc;
     a.rgb = first;
     a.rgb_stride = rgb->stride;
     a.rgb_frame_stride = rgb->frame_stride;
@@ -520,129 +576,60 @@ static int color_args(const dctq_rgb *rgb, const dctq_plane *y, const dctq_plane
     a.y = const_cast<uint8_t *>(y->pixels), a.y_stride = y->stride, a.y_frame_stride = y->frame_stride;
     a.cb = const_cast<uint8_t *>(cb->pixels), a.cb_stride = cb->stride, a.cb_frame_stride = cb->frame_stride;
     a.cr = const_cast<uint8_t *>(cr->pixels), a.cr_stride = cr->stride, a.cr_frame_stride = cr->frame_stride;
-    a.npatch = (uint32_t)(per_frame * y->nframes);
-    a.per_row = (uint32_t)per_row;
-    a.per_frame = (uint32_t)per_frame;
-    a.div_row = dctq::make_fastdiv(a.per_row);
-    a.div_frame = dctq::make_fastdiv(a.per_frame);
+    out->width = (uint32_t)rgb->width;
+    out->height = (uint32_t)rgb->height;
     *pixel_step = step;
     *s420 = half;
+    *aligned = whole && dwords && planar_dwords;
+    return DCTQ_OK;
+}
+
+// The four colour entry points: to_rgb is the direction, any_size as in color_args.
+static int color_planes(bool to_rgb, bool any_size, const dctq_rgb *rgb, const dctq_plane *y, const dctq_plane *cb,
+                        const dctq_plane *cr, void *stream) {
+    dctq::ColorPadArgs a;
+    int step;
+    bool s420, aligned;
+    if (int rc = color_args(rgb, y, cb, cr, any_size, &a, &step, &s420, &aligned)) return rc;
+    if (aligned)  // always, for the aligned entry points; for the others the same bytes from the same kernels
+        HIPCHK((to_rgb ? dctq::launch_ycc_to_rgb : dctq::launch_rgb_to_ycc)(a.c, step, s420, (hipStream_t)stream,
+                                                                           device_cus()),
+               to_rgb ? "ycc_to_rgb launch" : "rgb_to_ycc launch");
+    else
+        HIPCHK((to_rgb ? dctq::launch_ycc_to_rgb_crop : dctq::launch_rgb_to_ycc_pad)(a, step, s420, (hipStream_t)stream,
+                                                                                    device_cus()),
+               to_rgb ? "ycc_to_rgb_crop launch" : "rgb_to_ycc_pad launch");
     return DCTQ_OK;
 }
 
 int dctq_rgb_to_ycbcr_planes(const dctq_rgb *src, const dctq_plane *y, const dctq_plane *cb, const dctq_plane *cr,
                              void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntryRgbToYcbcrPlanes);
-    dctq::ColorArgs a;
-    int step;
-    bool s420;
-    if (int rc = color_args(src, y, cb, cr, &a, &step, &s420)) return rc;
-    HIPCHK(dctq::launch_rgb_to_ycc(a, step, s420, (hipStream_t)stream, device_cus()), "rgb_to_ycc launch");
-    return DCTQ_OK;
+    return color_planes(false, false, src, y, cb, cr, stream);
 }
 
 int dctq_ycbcr_to_rgb_planes(const dctq_plane *y, const dctq_plane *cb, const dctq_plane *cr, const dctq_rgb *dst,
                              void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntryYcbcrToRgbPlanes);
-    dctq::ColorArgs a;
-    int step;
-    bool s420;
-    if (int rc = color_args(dst, y, cb, cr, &a, &step, &s420)) return rc;
-    HIPCHK(dctq::launch_ycc_to_rgb(a, step, s420, (hipStream_t)stream, device_cus()), "ycc_to_rgb launch");
-    return DCTQ_OK;
-}
-
-// The same for the padding entry points: the RGB stack is the true W x H picture at any
-// alignment, the planes are its extension to whole blocks.  *aligned: the picture needs neither
-// padding nor unaligned access, so color_args describes the same call.
-static int color_pad_args(const dctq_rgb *rgb, const dctq_plane *y, const dctq_plane *cb, const dctq_plane *cr,
-                          dctq::ColorPadArgs *out, int *pixel_step, bool *s420, bool *aligned) {
-    if (!rgb || !rgb->pixels) return fail(DCTQ_EINVAL, "rgb/pixels is NULL");
-    const int step = rgb->pixel_step;
-    if (step != 1 && step != 3 && step != 4) return fail(DCTQ_EINVAL, "pixel_step must be 1, 3 or 4");
-    const long long cs = rgb->channel_stride;
-    if (step == 1 ? cs == 0 : (cs != 1 && cs != -1))
-        return fail(DCTQ_EINVAL, "channel_stride must be +1 or -1 (interleaved) or non-zero (planar)");
-    if (rgb->width < 1 || rgb->height < 1 || rgb->nframes < 1)
-        return fail(DCTQ_EINVAL, "rgb: width, height and nframes must be >= 1");
-    dctq::PlaneArgs py, pb, pr;
-    if (int rc = dctq::plane_args(y, &py)) return rc;
-    if (int rc = dctq::plane_args(cb, &pb)) return rc;
-    if (int rc = dctq::plane_args(cr, &pr)) return rc;
-    if (cb->width != cr->width || cb->height != cr->height) return fail(DCTQ_EINVAL, "Cb and Cr differ in size");
-    const bool full = cb->width == y->width && cb->height == y->height;
-    const bool half = 2ll * cb->width == y->width && 2ll * cb->height == y->height;
-    if (!full && !half)
-        return fail(DCTQ_EINVAL, "chroma must be luma's size (4:4:4) or exactly half of it in both directions (4:2:0)");
-    const long long m = half ? 16 : 8;
-    if (y->width != (rgb->width + m - 1) / m * m || y->height != (rgb->height + m - 1) / m * m)
-        return fail(DCTQ_EINVAL, "the Y plane is not the RGB stack's size rounded up to whole blocks (8, or 16 in 4:2:0)");
-    if (rgb->nframes != y->nframes || cb->nframes != y->nframes || cr->nframes != y->nframes)
-        return fail(DCTQ_EINVAL, "the RGB stack and the planes differ in nframes");
-    if (rgb->stride < (long long)rgb->width * step) return fail(DCTQ_EINVAL, "rgb: stride smaller than one row");
-    if (rgb->nframes > 1 && rgb->frame_stride < rgb->stride * (long long)rgb->height)
-        return fail(DCTQ_EINVAL, "rgb: frame_stride smaller than one frame");
-    if (step == 1 && (cs < 0 ? -cs : cs) < rgb->width) return fail(DCTQ_EINVAL, "rgb: channel_stride smaller than one row");
-    const long long per_row = y->width / 8, per_frame = per_row * (y->height / (half ? 2 : 1));
-    if (per_frame * y->nframes >= (1ll << 31)) return fail(DCTQ_EINVAL, "2^31 patches or more in one call");
-    // the lowest byte of pixel (0,0): its B byte when the order is B, G, R
-    uint8_t *first = (uint8_t *)rgb->pixels - (step != 1 && cs == -1 ? 2 : 0);
-    dctq::ColorArgs &a = out->c;
-    a = {};
-    a.rgb = first;
-    a.rgb_stride = rgb->stride;
-    a.rgb_frame_stride = rgb->frame_stride;
-    a.channel_stride = cs;
-    a.swap = step != 1 && cs == -1;
-    a.y = const_cast<uint8_t *>(y->pixels), a.y_stride = y->stride, a.y_frame_stride = y->frame_stride;
-    a.cb = const_cast<uint8_t *>(cb->pixels), a.cb_stride = cb->stride, a.cb_frame_stride = cb->frame_stride;
-    a.cr = const_cast<uint8_t *>(cr->pixels), a.cr_stride = cr->stride, a.cr_frame_stride = cr->frame_stride;
-    a.npatch = (uint32_t)(per_frame * y->nframes);
-    a.per_row = (uint32_t)per_row;
-    a.per_frame = (uint32_t)per_frame;
-    a.div_row = dctq::make_fastdiv(a.per_row);
-    a.div_frame = dctq::make_fastdiv(a.per_frame);
-    out->width = (uint32_t)rgb->width;
-    out->height = (uint32_t)rgb->height;
-    *pixel_step = step;
-    *s420 = half;
-    *aligned = rgb->width == y->width && rgb->height == y->height && ((uintptr_t)first) % 4 == 0 &&
-               rgb->stride % 4 == 0 && rgb->frame_stride % 4 == 0 && (step != 1 || cs % 4 == 0);
-    return DCTQ_OK;
+    return color_planes(true, false, dst, y, cb, cr, stream);
 }
 
 int dctq_rgb_to_ycbcr_pad_planes(const dctq_rgb *src, const dctq_plane *y, const dctq_plane *cb, const dctq_plane *cr,
                                  void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntryRgbToYcbcrPadPlanes);
-    dctq::ColorPadArgs a;
-    int step;
-    bool s420, aligned;
-    if (int rc = color_pad_args(src, y, cb, cr, &a, &step, &s420, &aligned)) return rc;
-    if (aligned)  // the same bytes from the kernels of the aligned entry point
-        HIPCHK(dctq::launch_rgb_to_ycc(a.c, step, s420, (hipStream_t)stream, device_cus()), "rgb_to_ycc launch");
-    else
-        HIPCHK(dctq::launch_rgb_to_ycc_pad(a, step, s420, (hipStream_t)stream, device_cus()), "rgb_to_ycc_pad launch");
-    return DCTQ_OK;
+    return color_planes(false, true, src, y, cb, cr, stream);
 }
 
 int dctq_ycbcr_to_rgb_crop_planes(const dctq_plane *y, const dctq_plane *cb, const dctq_plane *cr, const dctq_rgb *dst,
                                   void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntryYcbcrToRgbCropPlanes);
-    dctq::ColorPadArgs a;
-    int step;
-    bool s420, aligned;
-    if (int rc = color_pad_args(dst, y, cb, cr, &a, &step, &s420, &aligned)) return rc;
-    if (aligned)
-        HIPCHK(dctq::launch_ycc_to_rgb(a.c, step, s420, (hipStream_t)stream, device_cus()), "ycc_to_rgb launch");
-    else
-        HIPCHK(dctq::launch_ycc_to_rgb_crop(a, step, s420, (hipStream_t)stream, device_cus()), "ycc_to_rgb_crop launch");
-    return DCTQ_OK;
+    return color_planes(true, true, dst, y, cb, cr, stream);
 }
 
 int dctq_pad_planes(const dctq_plane *src, const dctq_plane *dst, int nplanes, void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntryPadPlanes);
     if (!src || !dst) return fail(DCTQ_EINVAL, "src/dst is NULL");
-    if (nplanes < 1 || nplanes > dctq::kMaxPlanes) return fail(DCTQ_EINVAL, "nplanes must be 1..4");
+    if (int rc = check_nplanes(nplanes)) return rc;
     dctq::PadSet ps = {};
     ps.n = nplanes;
     for (int k = 0; k < nplanes; ++k) {
@@ -650,24 +637,17 @@ int dctq_pad_planes(const dctq_plane *src, const dctq_plane *dst, int nplanes, v
         dctq::PlaneArgs pd;
         if (int rc = dctq::plane_args(&d, &pd)) return rc;
         if (!s.pixels) return fail(DCTQ_EINVAL, "src: pixels is NULL");
-        if (s.width < 1 || s.height < 1 || s.nframes < 1) return fail(DCTQ_EINVAL, "src: width, height and nframes must be >= 1");
-        if (s.stride < s.width) return fail(DCTQ_EINVAL, "src: stride smaller than one row");
-        if (s.nframes > 1 && s.frame_stride < s.stride * (long long)s.height)
-            return fail(DCTQ_EINVAL, "src: frame_stride smaller than one frame");
+        if (int rc = stack_geometry("src: ", true, s.width, s.height, s.nframes, s.width, s.stride, s.frame_stride))
+            return rc;
         if (d.width != (s.width + 7) / 8 * 8 || d.height != (s.height + 7) / 8 * 8 || d.nframes != s.nframes)
             return fail(DCTQ_EINVAL, "dst must be src's size rounded up to multiples of 8, with its nframes");
         for (int j = 0; j < nplanes; ++j)
             if (src[j].pixels == d.pixels) return fail(DCTQ_EINVAL, "src == dst: padding in place is not supported");
-        const long long per_row = d.width / 8, per_frame = per_row * d.height;
-        if (per_frame * d.nframes >= (1ll << 31)) return fail(DCTQ_EINVAL, "2^31 patches or more in one plane");
         dctq::PadPlane &p = ps.pl[k];
+        if (int rc = patch_grid(p, d.width / 8, d.height, d.nframes, "2^31 patches or more in one plane")) return rc;
         p.src = s.pixels, p.src_stride = s.stride, p.src_frame_stride = s.frame_stride;
         p.dst = const_cast<uint8_t *>(d.pixels), p.dst_stride = d.stride, p.dst_frame_stride = d.frame_stride;
         p.width = (uint32_t)s.width, p.height = (uint32_t)s.height;
-        p.per_row = (uint32_t)per_row, p.per_frame = (uint32_t)per_frame;
-        p.npatch = (uint32_t)(per_frame * d.nframes);
-        p.div_row = dctq::make_fastdiv(p.per_row);
-        p.div_frame = dctq::make_fastdiv(p.per_frame);
     }
     HIPCHK(dctq::launch_pad_planes(ps, (hipStream_t)stream, device_cus()), "pad_planes launch");
     return DCTQ_OK;

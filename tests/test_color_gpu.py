@@ -253,6 +253,21 @@ def test_refusals(T, dm):
         "NULL Cr pixels": dict(cr=dict(pixels=None)),
         "plane width not a multiple of 8": dict(rgb_kw=dict(width=28), y=dict(width=28), cb=dict(width=14),
                                                 cr=dict(width=14)),
+        "frame_stride below a frame": dict(rgb_kw=dict(frame_stride=3 * w * h - 4)),
+        "planar channel_stride 0": dict(rgb_kw=dict(pixel_step=1, stride=w, frame_stride=w * h, channel_stride=0)),
+        "planar channel_stride below a row": dict(rgb_kw=dict(pixel_step=1, stride=w, frame_stride=w * h,
+                                                              channel_stride=w - 4)),
+        "planar channel_stride below a row, B first": dict(rgb_kw=dict(pixel_step=1, stride=w, frame_stride=w * h,
+                                                                       channel_stride=4 - w)),
+        "picture width 0": dict(rgb_kw=dict(width=0)),
+        "picture nframes 0": dict(rgb_kw=dict(nframes=0)),
+        # what the any-size entry points take: 17 x 9 with planes of whole blocks
+        "a 17 x 9 picture": dict(rgb_kw=dict(width=17, height=9), y=dict(height=16), cb=dict(height=8),
+                                 cr=dict(height=8)),
+        # 4:4:4, 2^28 blocks a plane but 2^31 patches: refused before anything is touched
+        "2^31 patches": dict(rgb_kw=dict(width=1 << 16, height=1 << 16, nframes=4, stride=3 << 16, frame_stride=3 << 32),
+                             **{p: dict(width=1 << 16, height=1 << 16, nframes=4, stride=1 << 16, frame_stride=1 << 32)
+                                for p in ("y", "cb", "cr")}),
     }
     for name, kw in cases.items():
         assert call(**kw) == (EINVAL, EINVAL), name

@@ -306,6 +306,16 @@ def test_refusals(T, dm):
         "NULL Cr plane": dict(null=2),
         "NULL Cb pixels": dict(cb=dict(pixels=None)),
         "a misaligned plane": dict(y=dict(pixels=big[0].data_ptr() + 4)),
+        "nframes 0": dict(rgb_kw=dict(nframes=0)),
+        "pixel_step 0": dict(rgb_kw=dict(pixel_step=0)),
+        "planar channel_stride below a row": dict(rgb_kw=dict(pixel_step=1, stride=w, frame_stride=w * h,
+                                                              channel_stride=w - 1)),
+        "planar channel_stride below a row, B first": dict(rgb_kw=dict(pixel_step=1, stride=w, frame_stride=w * h,
+                                                                       channel_stride=1 - w)),
+        # 4:4:4, 2^28 blocks a plane but 2^31 patches: refused before anything is touched
+        "2^31 patches": dict(rgb_kw=dict(width=65529, height=65529, nframes=4, stride=3 << 16, frame_stride=3 << 32),
+                             **{p: dict(width=1 << 16, height=1 << 16, nframes=4, stride=1 << 16, frame_stride=1 << 32)
+                                for p in ("y", "cb", "cr")}),
     }
     for name, kw in cases.items():
         assert call(**kw) == (EINVAL, EINVAL), name
@@ -336,6 +346,16 @@ def test_refusals(T, dm):
         "src width 0": dict(s=dict(width=0)),
         "src stride below a row": dict(s=dict(stride=12)),
         "dst misaligned": dict(d=dict(pixels=dst.data_ptr() + 1)),
+        "src == dst of another plane": dict(n=2, s=dict(pixels=dst[1].data_ptr())),
+        "dst rounded down": dict(d=dict(width=8)),
+        "dst too tall": dict(d=dict(height=16, frame_stride=16 * 16)),
+        "dst with more frames": dict(d=dict(nframes=2)),
+        "src height 0": dict(s=dict(height=0)),
+        "src nframes 0": dict(s=dict(nframes=0)),
+        "src frame_stride below a frame": dict(s=dict(nframes=2, frame_stride=13 * 5 - 1), d=dict(nframes=2)),
+        # 2^28 blocks but 2^31 patches: refused before anything is touched
+        "2^31 patches": dict(s=dict(width=65529, height=65529, nframes=4, stride=1 << 16, frame_stride=1 << 32),
+                             d=dict(width=1 << 16, height=1 << 16, nframes=4, stride=1 << 16, frame_stride=1 << 32)),
     }
     for name, kw in pads.items():
         assert pad(**kw) == EINVAL, name
@@ -351,6 +371,39 @@ def test_refusals(T, dm):
           dm._Plane(big[2].data_ptr(), 16, 16 * 12, 12, 12, 1)]
     assert L.dctq_rgb_to_ycbcr_planes(C.byref(r), *map(C.byref, pl), None) == EINVAL
     assert L.dctq_ycbcr_to_rgb_planes(*map(C.byref, pl), C.byref(r), None) == EINVAL
+
+    # one rule at a time: what the any-size entry points take and the aligned ones refuse
+    pic = T.zeros(1024, dtype=T.uint8, device="cuda")
+
+    def four(sub, w=None, h=None, **rgb_kw):
+        """(any-size forward, inverse, aligned forward, inverse) on one frame of whole blocks, 16 x 16
+        in 4:2:0 or 8 x 8 in 4:4:4, that all four take until the overrides are applied; w x h: the
+        picture's size when its planes are its extension."""
+        m, s = (16, 2) if sub == "420" else (8, 1)
+        w, h = w or m, h or m
+        ew, eh = ext(w, m), ext(h, m)
+        r = dm._Rgb(pic.data_ptr(), 3 * w + (-3 * w) % 4, 0, 1, 3, w, h, 1)
+        for k, v in rgb_kw.items():
+            setattr(r, k, v)
+        pl = [C.byref(dm._Plane(big[k].data_ptr(), ew // d, 0, ew // d, eh // d, 1)) for k, d in enumerate((1, s, s))]
+        rcs = (L.dctq_rgb_to_ycbcr_pad_planes(C.byref(r), *pl, None), L.dctq_ycbcr_to_rgb_crop_planes(*pl, C.byref(r), None),
+               L.dctq_rgb_to_ycbcr_planes(C.byref(r), *pl, None), L.dctq_ycbcr_to_rgb_planes(*pl, C.byref(r), None))
+        T.cuda.synchronize()
+        return rcs
+
+    only_any_size = (0, 0, EINVAL, EINVAL)
+    for sub, n in (("420", 16), ("444", 8)):
+        assert four(sub) == (0, 0, 0, 0), sub
+        assert four(sub, pixels=pic.data_ptr() + 1) == only_any_size, sub
+        assert four(sub, pixels=pic.data_ptr() + 4, channel_stride=-1) == only_any_size, sub  # B at +2
+        assert four(sub, pixels=pic.data_ptr() + 2, channel_stride=-1) == (0, 0, 0, 0), sub
+        assert four(sub, stride=3 * n + 2) == only_any_size, sub
+        assert four(sub, frame_stride=2) == only_any_size, sub
+        planar = dict(pixel_step=1, stride=n)
+        assert four(sub, channel_stride=n * n, **planar) == (0, 0, 0, 0), sub
+        assert four(sub, channel_stride=n * n + 2, **planar) == only_any_size, sub
+        assert four(sub, w=17, h=9) == only_any_size, sub                                    # 32 x 16 or 24 x 16 planes
+        assert four(sub, w=n - 1) == only_any_size, sub
 
     # the same from Python
     ok = T.zeros((f, h, w, 3), dtype=T.uint8, device="cuda")
