@@ -31,6 +31,11 @@ class _Plane(C.Structure):
                 ("width", C.c_int), ("height", C.c_int), ("nframes", C.c_int)]
 
 
+class _Window(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("nframes", C.c_int),
+                ("x0", C.c_int), ("y0", C.c_int), ("frame0", C.c_int)]
+
+
 class _Rgb(C.Structure):
     _fields_ = [("pixels", C.c_void_p), ("stride", C.c_longlong), ("frame_stride", C.c_longlong),
                 ("channel_stride", C.c_longlong), ("pixel_step", C.c_int),
@@ -104,6 +109,7 @@ def _bind(L: C.CDLL, diagnostic: bool) -> C.CDLL:
         "dctq_bits_pack": ([vp, i, vp, ll, vp, vp, ll, vp, vp], i),
         "dctq_bits_decode": ([vp, vp, ll, vp, vp], i),
         "dctq_decode_bits_planes": ([vp, vp, vp, vp, C.POINTER(_Plane), i, vp], i),
+        "dctq_decode_bits_window_planes": ([vp, vp, vp, vp, C.POINTER(_Window), C.POINTER(_Plane), i, vp], i),
         "dctq_block_lengths": ([vp, ll, i, vp, vp, vp], i),
         "dctq_block_offsets_workspace_bytes": ([ll], C.c_size_t),
         "dctq_block_offsets": ([vp, i, ll, vp, vp, vp], i),
@@ -654,6 +660,62 @@ class Plan:
         self._chk(self._L.dctq_decode_bits_planes(
             self._h, C.c_void_p(bytes.data_ptr()), C.c_void_p(offsets.data_ptr()),
             C.cast(vp, C.c_void_p) if vp is not None else None, descs, n, _stream_ptr(stream)))
+        return outs
+
+    def decode_bits_window(self, bytes, offsets, shapes, windows, outs=None, var_nums=None, stream=None):
+        """A window of every plane of a "bits v1" stream -> u8 pixels in ONE launch that reads
+        only the blocks inside the windows (dctq_decode_bits_window_planes).  shapes[k] is the
+        STORED (F, H, W) or (H, W) of plane k, what bytes / offsets (the whole stream's, as for
+        decode_bits) are numbered over; windows[k] = ((f0, f1), (y0, y1), (x0, x1)), half-open,
+        y and x in pixels and multiples of 8.  Returns the list of u8 tensors [f1 - f0, y1 - y0,
+        x1 - x0], each bit for bit decode_bits(bytes, offsets, shapes=shapes, ...)[k][f0:f1,
+        y0:y1, x0:x1].  outs, if given, are the windows' own tensors and may be strided views
+        (bytes outside them are not touched); var_nums[k] (adaptive plans) is the whole stored
+        plane's.  The work unit is a run of up to 64 blocks of one window row
+        (tools/window_ref.py): a window narrower than 512 pixels leaves part of each wave idle."""
+        import torch
+        if not isinstance(bytes, torch.Tensor) or not bytes.is_cuda or bytes.dtype != torch.uint8:
+            raise DctqError("bytes must be a uint8 tensor on a HIP device")
+        if not bytes.is_contiguous():
+            raise DctqError("bytes must be contiguous")
+        n = len(shapes)
+        if len(windows) != n:
+            raise DctqError(f"windows needs one entry per plane ({n}), got {len(windows)}")
+        shapes = [(1, *map(int, s)) if len(s) == 2 else tuple(map(int, s)) for s in shapes]
+        if any(len(s) != 3 for s in shapes):
+            raise DctqError("shapes entries must be (F, H, W) or (H, W)")
+        wins, wshapes = [], []
+        for k, ((f, h, w), win) in enumerate(zip(shapes, windows)):
+            try:
+                (f0, f1), (y0, y1), (x0, x1) = [tuple(map(int, r)) for r in win]
+            except (TypeError, ValueError):
+                raise DctqError(f"windows[{k}] must be ((f0, f1), (y0, y1), (x0, x1))") from None
+            if f < 1 or h < 8 or w < 8 or h % 8 or w % 8:
+                raise DctqError(f"shapes[{k}] {(f, h, w)}: height and width must be multiples of 8, nframes >= 1")
+            if not (0 <= f0 < f1 <= f and 0 <= y0 < y1 <= h and 0 <= x0 < x1 <= w):
+                raise DctqError(f"windows[{k}] {win} is empty or leaves the stored plane {(f, h, w)}")
+            if y0 % 8 or y1 % 8 or x0 % 8 or x1 % 8:
+                raise DctqError(f"windows[{k}] {win}: rows and columns must be multiples of 8")
+            wins.append(_Window(w, h, f, x0, y0, f0))
+            wshapes.append((f1 - f0, y1 - y0, x1 - x0))
+        nbs = [f * (h // 8) * (w // 8) for f, h, w in shapes]
+        if sum(nbs) >= 1 << 26:
+            raise DctqError("more than 2^26 - 1 blocks in one decode")
+        outs, descs, _ = _decode_outs("decode_bits_window", n, wshapes, outs, None, [bytes.device] * n)
+        _need_byte_offsets(offsets, sum(nbs), bytes)
+        if any(o.device != bytes.device for o in outs):
+            raise DctqError("bytes, offsets and outs must be on one device")
+        if self.adaptive and var_nums is None:
+            raise DctqError("adaptive decode needs var_nums")
+        if var_nums is not None:
+            if len(var_nums) != n:
+                raise DctqError(f"var_nums needs one entry per plane ({n}), got {len(var_nums)}")
+            for k, v in enumerate(var_nums):
+                _need(v, nbs[k], torch.int32, f"var_nums[{k}]", bytes.device)
+        vp = (C.c_void_p * n)(*[v.data_ptr() for v in var_nums]) if var_nums is not None else None
+        self._chk(self._L.dctq_decode_bits_window_planes(
+            self._h, C.c_void_p(bytes.data_ptr()), C.c_void_p(offsets.data_ptr()),
+            C.cast(vp, C.c_void_p) if vp is not None else None, (_Window * n)(*wins), descs, n, _stream_ptr(stream)))
         return outs
 
     def encode_bits_planes(self, planes, outs=None, capacity=None, stream=None, symbol_bytes=None):
@@ -1273,17 +1335,99 @@ def compress(src, quality: int = 50, adaptive: bool = False, subsampling: str = 
     return frame_pack(packed, boff, shapes, plan.quality, adaptive, var_nums, colour, stream=stream, crops=crops)
 
 
-def decompress(buf, channels: int = 3, planar: bool = False, bgr: bool = False, stream=None):
+def _pair(r, what):
+    """(a, b) as two ints, or DctqError."""
+    try:
+        a, b = r
+        return int(a), int(b)
+    except (TypeError, ValueError):
+        raise DctqError(f"{what} must be a pair of integers, got {r!r}") from None
+
+
+def _region_windows(shapes, crops, colour, region, frames):
+    """decompress's region arithmetic, on the host: the stored shapes [(F, H, W)] and crops
+    [(pad_bottom, pad_right)] or None of a container, a region in pixels of the TRUE picture
+    (or None: all of it; plain planes: one region, or a list of one per plane) and frames
+    (f0, f1) or None -> (windows, cuts): windows[k] = ((f0, f1), (Y0, Y1), (X0, X1)) of stored
+    plane k for Plan.decode_bits_window, the region grown to multiples of m (8; 16 in the luma
+    of a 4:2:0 picture, whose chroma windows are half of it), and cuts[k] = (dy, dx, h, w):
+    where the region sits inside the window's picture (colour: one cut, the picture's).
+    DctqError for a region or frame range that is empty or leaves the true picture, and for
+    anything else that is not what the container's kind takes."""
+    crops = crops or [(0, 0)] * len(shapes)
+    true = [(h - pb, w - pr) for (_, h, w), (pb, pr) in zip(shapes, crops)]
+    nf = min(f for f, _, _ in shapes)
+    f0, f1 = (0, nf) if frames is None else _pair(frames, "frames")
+    if not 0 <= f0 < f1 <= nf:
+        raise DctqError(f"frames {(f0, f1)} is empty or outside the {nf} frames")
+    npic = 1 if colour else len(shapes)
+    if region is None:
+        regions = [((0, h), (0, w)) for h, w in true[:npic]]
+    else:
+        try:
+            single = not hasattr(region[0][0], "__len__")
+        except (TypeError, IndexError):
+            raise DctqError("region must be ((y0, y1), (x0, x1))" + ("" if colour else ", or a list of one per plane")) from None
+        if single:
+            if len(set(true[:npic])) != 1:
+                raise DctqError("the planes differ in size: region must be a list of one region per plane")
+            regions = [region] * npic
+        elif colour or len(region) != npic:
+            raise DctqError(f"region must be ((y0, y1), (x0, x1))" + ("" if colour else f", or a list of {npic} of them"))
+        else:
+            regions = list(region)
+    sub = 2 if colour and shapes[1][1:] != shapes[0][1:] else 1
+    m = 8 * sub
+    windows, cuts = [], []
+    for k, (r, (th, tw)) in enumerate(zip(regions, true)):
+        if not hasattr(r, "__len__") or len(r) != 2:
+            raise DctqError(f"region {r!r} must be ((y0, y1), (x0, x1))")
+        (y0, y1), (x0, x1) = _pair(r[0], "a region's rows"), _pair(r[1], "a region's columns")
+        if not (0 <= y0 < y1 <= th and 0 <= x0 < x1 <= tw):
+            raise DctqError(f"region {((y0, y1), (x0, x1))} is empty or outside the picture of {th} x {tw}")
+        ya, xa = y0 // m * m, x0 // m * m
+        yb, xb = -(-y1 // m) * m, -(-x1 // m) * m   # inside the stored plane: it is whole multiples of m
+        windows.append(((f0, f1), (ya, yb), (xa, xb)))
+        cuts.append((y0 - ya, x0 - xa, y1 - y0, x1 - x0))
+    if colour:
+        (_, (ya, yb), (xa, xb)) = windows[0]
+        windows += [((f0, f1), (ya // sub, yb // sub), (xa // sub, xb // sub))] * 2
+    return windows, cuts
+
+
+def decompress(buf, channels: int = 3, planar: bool = False, bgr: bool = False, stream=None, region=None, frames=None):
     """The inverse of compress: frame_unpack, the container's plan, Plan.decode_bits and, for a
     colour container, ycbcr_to_rgb (channels / planar / bgr as there).  Returns the RGB stack
     [F, H, W, channels] for a colour container, the list of u8 planes [F, H, W] otherwise.
     Nothing is decoded from a container that frame_unpack refuses.  A frame c1 container comes
     back at its true size: the picture through ycbcr_to_rgb(size=(H, W)); plain planes as the
-    [:, :H, :W] VIEWS of the decoded (padded) planes, which are therefore not contiguous."""
+    [:, :H, :W] VIEWS of the decoded (padded) planes, which are therefore not contiguous.
+    region=((y0, y1), (x0, x1)), in pixels of the TRUE picture at any alignment, and / or
+    frames=(f0, f1), both half-open: only that part, byte for byte decompress(buf, ...)[f0:f1,
+    y0:y1, x0:x1], for frame v1 and frame c1 alike, decoded from the blocks it needs and no
+    others (Plan.decode_bits_window over the enclosing window of whole blocks -- of 16 x 16
+    luma pixels for a 4:2:0 picture; chroma upsampling is nearest neighbour, so the window
+    converts exactly as the whole picture does).  The result may be a VIEW into the window's
+    picture (a region that does not start on a block), so it need not be contiguous.  Plain
+    planes take one region when all planes have one true size, else a list of one region per
+    plane; frames must lie inside every plane's.  A region or frame range that is empty or
+    leaves the true picture raises DctqError before anything is decoded.  With neither given
+    the path and the result are those described first."""
     d = frame_unpack(buf, stream=stream)
     plan = _frame_plan(d["quality"], d["adaptive"], d["bytes"].device)
-    outs = plan.decode_bits(d["bytes"], d["offsets"], shapes=d["shapes"], var_nums=d["var_nums"], stream=stream)
     crops = d["crops"]
+    if region is not None or frames is not None:
+        windows, cuts = _region_windows(d["shapes"], crops, d["colour"], region, frames)
+        outs = plan.decode_bits_window(d["bytes"], d["offsets"], d["shapes"], windows, var_nums=d["var_nums"],
+                                       stream=stream)
+        if not d["colour"]:
+            return [o[:, dy:dy + h, dx:dx + w] for o, (dy, dx, h, w) in zip(outs, cuts)]
+        dy, dx, h, w = cuts[0]
+        whole = (dy + h, dx + w) == tuple(outs[0].shape[1:])
+        rgb = ycbcr_to_rgb(*outs, channels=channels, planar=planar, bgr=bgr, stream=stream,
+                           size=None if whole else (dy + h, dx + w))
+        return rgb[:, dy:, dx:] if dy or dx else rgb
+    outs = plan.decode_bits(d["bytes"], d["offsets"], shapes=d["shapes"], var_nums=d["var_nums"], stream=stream)
     if not d["colour"]:
         if crops is None:
             return outs

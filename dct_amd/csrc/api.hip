@@ -322,6 +322,69 @@ int dctq_decode_bits_planes(const dctq_plan *plan, const uint8_t *bytes, const u
     return DCTQ_OK;
 }
 
+// The window decoder's planes: dst[k] placed in the stored plane win[k] describes, the stored
+// planes' concatenated block numbering and the run numbering (tools/window_ref.py).  Needs no
+// plan and no device, so every refusal of the geometry comes before either is looked at.
+static int window_set(const dctq_window *win, const dctq_plane *dst, int nplanes, dctq::WindowSet *out) {
+    if (!win || !dst) return fail(DCTQ_EINVAL, "win/dst is NULL");
+    if (int rc = check_nplanes(nplanes)) return rc;
+    dctq::WindowSet &ws = *out;
+    ws = {};
+    ws.n = nplanes;
+    long long blocks = 0, runs = 0;
+    for (int k = 0; k < nplanes; ++k) {
+        const dctq_window &w = win[k];
+        if (w.width <= 0 || w.height <= 0 || w.width % 8 || w.height % 8)
+            return fail(DCTQ_EINVAL, "window: the stored width and height must be positive multiples of 8");
+        if (w.nframes < 1) return fail(DCTQ_EINVAL, "window: the stored nframes must be >= 1");
+        if (w.x0 < 0 || w.y0 < 0 || w.x0 % 8 || w.y0 % 8)
+            return fail(DCTQ_EINVAL, "window: x0 and y0 must be non-negative multiples of 8");
+        if (w.frame0 < 0) return fail(DCTQ_EINVAL, "window: frame0 must be >= 0");
+        dctq::PlaneArgs &p = ws.pl[k];
+        if (int rc = dctq::plane_args(&dst[k], &p)) return rc;
+        if ((long long)w.x0 + dst[k].width > w.width || (long long)w.y0 + dst[k].height > w.height)
+            return fail(DCTQ_EINVAL, "window: the region leaves the stored plane");
+        if ((long long)w.frame0 + dst[k].nframes > w.nframes)
+            return fail(DCTQ_EINVAL, "window: the frame range leaves the stored frames");
+        const long long sbw = w.width / 8, sper = sbw * (w.height / 8);
+        if (blocks + sper * w.nframes >= 1ll << 26) return fail(DCTQ_EINVAL, "more than 2^26 - 1 blocks in one decode");
+        dctq::WindowPlane &wp = ws.win[k];
+        wp.var_first = (uint32_t)(w.frame0 * sper + (w.y0 / 8) * sbw + w.x0 / 8);
+        wp.first = (uint32_t)blocks + wp.var_first;
+        wp.bw = (uint32_t)sbw;
+        wp.nblk_frame = (uint32_t)sper;
+        wp.rows = (uint32_t)(p.nblk_frame / p.bw);
+        wp.runs_row = (uint32_t)((p.bw + 63) / 64);
+        wp.div_runs = dctq::make_fastdiv(wp.runs_row);
+        wp.div_rows = dctq::make_fastdiv(wp.rows);
+        ws.run_first[k] = (uint32_t)runs;
+        blocks += sper * w.nframes;
+        runs += (long long)wp.runs_row * wp.rows * dst[k].nframes;  // at most the window's blocks: < 2^26
+    }
+    for (int k = nplanes; k <= dctq::kMaxPlanes; ++k) ws.run_first[k] = (uint32_t)runs;
+    return DCTQ_OK;
+}
+
+int dctq_decode_bits_window_planes(const dctq_plan *plan, const uint8_t *bytes, const uint32_t *offsets,
+                                   const int32_t *const *var_num, const dctq_window *win, const dctq_plane *dst,
+                                   int nplanes, void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryDecodeBitsWindowPlanes);
+    dctq::WindowSet ws;
+    if (int rc = window_set(win, dst, nplanes, &ws)) return rc;
+    if (int rc = dctq::check_plan(plan)) return rc;
+    if (!bytes || !offsets) return fail(DCTQ_EINVAL, "bytes/offsets is NULL");
+    if (misaligned(offsets, 4)) return fail(DCTQ_EINVAL, "offsets must be 4-byte aligned");
+    if (plan->adaptive && !var_num) return fail(DCTQ_EINVAL, "adaptive decode needs var_num");
+    for (int k = 0; k < nplanes; ++k) {
+        if (plan->adaptive && !var_num[k]) return fail(DCTQ_EINVAL, "adaptive decode needs every var_num[k]");
+        ws.var[k] = plan->adaptive ? var_num[k] : nullptr;
+    }
+    HIPCHK(dctq::launch_decode_bits_window(ws, bytes, offsets, plan->dev, plan->adaptive, plan->inv_f32 != 0,
+                                           (hipStream_t)stream, plan->num_cus),
+           "decode_bits_window launch");
+    return DCTQ_OK;
+}
+
 int dctq_synth(uint64_t seed, int kind, const dctq_plane *dst, void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntrySynth);
     if (!dst || !dst->pixels) return fail(DCTQ_EINVAL, "dst is NULL");

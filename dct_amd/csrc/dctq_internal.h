@@ -67,8 +67,9 @@ enum Entry : int {
     kEntryRgbToYcbcrPadPlanes,
     kEntryYcbcrToRgbCropPlanes,
     kEntryPadPlanes,
+    kEntryDecodeBitsWindowPlanes,
 };
-static_assert(kEntryPadPlanes < 32, "LaunchIsolation keeps one bit per entry point in a uint32_t");
+static_assert(kEntryDecodeBitsWindowPlanes < 32, "LaunchIsolation keeps one bit per entry point in a uint32_t");
 class LaunchIsolation {
   public:
     LaunchIsolation(const void *stream, Entry entry);
@@ -261,6 +262,26 @@ struct SymbolSet {
     int n;
 };
 
+// The window decoder's planes (decode_window.hip): pl[k].src is the DESTINATION, the window's
+// own picture, so pl[k].bw is the window's width in blocks; win[k] places it in the stored
+// plane.  A run is up to 64 consecutive stored blocks of one window row (tools/window_ref.py);
+// runs are numbered over window rows, frames, planes.
+struct WindowPlane {
+    uint32_t first;       // the window's first block in the concatenated stored numbering (offsets' index)
+    uint32_t var_first;   // ... and inside its stored plane (var_num's index)
+    uint32_t bw, nblk_frame;  // the STORED plane's blocks per row and per frame
+    uint32_t rows;        // the window's block rows per frame
+    uint32_t runs_row;    // runs per window row: ceil(pl[k].bw / 64)
+    FastDiv div_runs, div_rows;  // by runs_row and by rows
+};
+struct WindowSet {
+    PlaneArgs pl[kMaxPlanes];
+    const int32_t *var[kMaxPlanes];        // adaptive plans: all set (the whole stored plane's); otherwise unused
+    WindowPlane win[kMaxPlanes];
+    uint32_t run_first[kMaxPlanes + 1];    // each plane's first run; run_first[n..] = total (< 2^26)
+    int n;
+};
+
 // The colour kernels' arguments (color.hip): an RGB picture stack and its Y, Cb, Cr planes.
 // A patch is 8 pixels by 2 rows (4:2:0) or 1 row (4:4:4); patches are numbered in raster
 // order over the frames, npatch < 2^31.
@@ -403,6 +424,10 @@ hipError_t launch_bits_decode(const uint8_t *bytes, const uint32_t *offsets, lon
                               hipStream_t stream, int num_cus);
 hipError_t launch_decode_bits(const SymbolSet &ss, const uint8_t *bytes, const uint32_t *offsets, const DevTables *dev,
                               int adaptive, bool inv_f32, hipStream_t stream, int num_cus);
+// ... and a window of those planes: a block region and a frame range of each (decode_window.hip)
+hipError_t launch_decode_bits_window(const WindowSet &ws, const uint8_t *bytes, const uint32_t *offsets,
+                                     const DevTables *dev, int adaptive, bool inv_f32, hipStream_t stream,
+                                     int num_cus);
 // byte offsets of a packed stream <-> one or two bytes of length per block (frame.hip); ws: rle_workspace_bytes(nblk)
 hipError_t launch_block_lengths(const uint32_t *offsets, long long nblk, int length_bytes, void *lengths,
                                 uint32_t *max_length, hipStream_t stream, int num_cus);

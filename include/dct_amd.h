@@ -316,6 +316,43 @@ int dctq_bits_decode(const uint8_t *bytes, const uint32_t *offsets, long long nb
 int dctq_decode_bits_planes(const dctq_plan *plan, const uint8_t *bytes, const uint32_t *offsets,
                             const int32_t *const *var_num, const dctq_plane *dst, int nplanes, void *stream);
 
+/* Random access into a packed stream: a block region and a frame range of every
+ * plane -> u8 pixels in ONE launch, reading only the blocks inside the windows
+ * (every block of bits v1 has its own byte offset).  win[k] places dst[k] in
+ * stored plane k; dst[k] is the window's own picture, so its width x height x
+ * nframes is the window's extent (as every decoder destination: multiples of 8,
+ * pixels 8-byte aligned, any stride).  offsets is the WHOLE stream's N + 1 entries,
+ * N = the blocks of the stored geometries in win, numbered plane by plane;
+ * var_num[k] (adaptive plans) is the whole stored plane's array.  The contract is
+ * an equivalence: the pixels are, bit for bit, what
+ *   dctq_decode_bits_planes(plan, bytes, offsets, var_num, full, nplanes)
+ * writes into full planes of the stored geometries, copied out of
+ *   [frame0, frame0 + nframes) x [y0, y0 + height) x [x0, x0 + width)
+ * of each -- for any bytes and any non-decreasing offsets.  Bytes of dst outside
+ * width x height of each frame are not touched.
+ *   Runs.  The work unit is a run: up to 64 consecutive stored blocks of one block
+ *   row of one frame of one plane, inside that plane's window; a window wb blocks
+ *   wide has ceil(wb / 64) runs per block row, numbered over window rows, frames,
+ *   planes (tools/window_ref.py states the mapping in plain Python).  A run of nb
+ *   blocks from stored block s0 reads offsets[s0 .. s0 + nb] and nothing outside
+ *   [offsets[s0], offsets[s0 + nb]) of the bytes: no payload byte of a block that
+ *   is in no run is read.  A window narrower than 64 blocks leaves part of each
+ *   wave idle.
+ * DCTQ_EINVAL, before any launch: NULL win or dst; a stored width or height that
+ * is not a positive multiple of 8, or stored nframes < 1; x0 or y0 negative or not
+ * a multiple of 8, frame0 < 0; a window that leaves the stored plane or a frame
+ * range that leaves the stored frames; N >= 2^26; nplanes outside 1..4; a dst
+ * that dctq_decode_bits_planes would refuse; a NULL plan, bytes or offsets;
+ * missing var_num on an adaptive plan.  The geometry is checked first and needs
+ * no device.  Asynchronous on stream; allocates nothing. */
+typedef struct dctq_window {
+    int width, height, nframes;   /* the STORED plane: what the stream's blocks are numbered over */
+    int x0, y0, frame0;           /* first pixel column and row (multiples of 8) and first frame of the window */
+} dctq_window;
+int dctq_decode_bits_window_planes(const dctq_plan *plan, const uint8_t *bytes, const uint32_t *offsets,
+                                   const int32_t *const *var_num, const dctq_window *win,
+                                   const dctq_plane *dst, int nplanes, void *stream);
+
 /* Self-contained container, format "frame v1": everything a decoder of a "bits
  * v1" stream needs, in one byte buffer (tools/frame_ref.py states it in plain
  * Python).  Little-endian.  A block of bits v1 is at most 368 B, so the N + 1
