@@ -244,6 +244,19 @@ def _stream_ptr(stream=None):
     return C.c_void_p(s.cuda_stream)
 
 
+def _on_stream(stream):
+    """torch's own copies and fills go to `stream` too (None: the current one)."""
+    import torch
+    return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+
+
+def _read_back(t, stream):
+    """A small int32 device tensor of uint32 bit patterns (offsets, totals) as a list of ints:
+    copied on `stream` (None: the current one), so after the launches sent there (one sync)."""
+    with _on_stream(stream):
+        return [v & 0xFFFFFFFF for v in t.cpu().tolist()]
+
+
 def plane_desc(px, width: int = None, height: int = None):
     """Describe a uint8 CUDA tensor [H, W] or [F, H, W] (rows may be padded: stride = px.stride(-2))."""
     import torch
@@ -256,6 +269,76 @@ def plane_desc(px, width: int = None, height: int = None):
     f, h, w = px.shape
     return _Plane(px.data_ptr(), px.stride(1), px.stride(0) if f > 1 else px.stride(1) * h,
                   width if width is not None else w, height if height is not None else h, f)
+
+
+def _nblocks(d) -> int:
+    """The 8 x 8 blocks of a _Plane, or of an (F, H, W) shape."""
+    if isinstance(d, _Plane):
+        return d.nframes * (d.width // 8) * (d.height // 8)
+    f, h, w = d
+    return f * (h // 8) * (w // 8)
+
+
+def _whole_blocks(f, h, w) -> bool:
+    """A stored plane is whole blocks and has at least one frame."""
+    return f >= 1 and h >= 8 and w >= 8 and not (h % 8 or w % 8)
+
+
+def _plane_set(planes):
+    """(n, descs, nbs) of a list of source planes: the _Plane array a `const dctq_plane *`
+    parameter takes and each plane's block count."""
+    n = len(planes)
+    descs = (_Plane * n)(*[plane_desc(px) for px in planes])
+    return n, descs, [_nblocks(d) for d in descs]
+
+
+def _ptr(t):
+    """A tensor (or None) as a `void *` argument (or NULL)."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _ptrs(ts):
+    """A list of tensors (or None) as a `void *const *` argument (or NULL): the ctypes array
+    itself, which owns the pointers and lives as long as the argument list it stands in."""
+    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts]) if ts is not None else None
+
+
+def _per_plane(outs, nbs, per, dtype, planes, device=None):
+    """The per-plane outputs of a multi-plane call: outs as given, or [nb_k, per] tensors of
+    dtype beside each plane (or all on device).  _need_planes checks either."""
+    import torch
+    if outs is None:
+        outs = [torch.empty((nb, per), dtype=dtype, device=device or px.device) for nb, px in zip(nbs, planes)]
+    return outs
+
+
+def _out(out, shape, dtype, device):
+    """The one result of a call: out as given, or a new tensor of shape beside the input; checked
+    either way (_need), which is what refuses an input that is not on a device."""
+    import math
+    import torch
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=device)
+    return _need(out, math.prod(shape), dtype, "out", device)
+
+
+def _workspace(bytes_fn, n, device):
+    """The scratch of an n-block call whose size dctq_*_workspace_bytes (bytes_fn) states."""
+    import torch
+    return torch.empty(int(bytes_fn(n)) // 4 + 1, dtype=torch.int32, device=device)
+
+
+def _shapes3(shapes):
+    """shapes entries (F, H, W) or (H, W) -> [(F, H, W)] of ints."""
+    shapes = [(1, *map(int, s)) if len(s) == 2 else tuple(map(int, s)) for s in shapes]
+    if any(len(s) != 3 for s in shapes):
+        raise DctqError("shapes entries must be (F, H, W) or (H, W)")
+    return shapes
+
+
+def _clamp_quality(q) -> int:
+    """A quality as the plan clamps it (1..100)."""
+    return min(max(int(q), 1), 100)
 
 
 def _need_planes(outs, var_nums, recons, nbs, planes):
@@ -272,11 +355,11 @@ def _need_planes(outs, var_nums, recons, nbs, planes):
             _need(t, nb * per, dt, f"{name}[{k}]", px.device)
 
 
-def _decode_outs(what, n, shapes, outs, var_nums, devices):
-    """The destination planes of decode_planes / decode_symbols: (outs, descs, nbs).  shapes[k]
-    is (F, H, W) or (H, W); outs[k], if given, a u8 tensor [F, H, W] or [H, W], possibly a
-    strided view; one of the two is needed, and both must agree.  var_nums[k], if given, is
-    sized for plane k's blocks.  devices[k]: where outs[k] is allocated."""
+def _decode_outs(what, n, shapes, outs, var_nums, devices, var_nbs=None):
+    """The destination planes of decode_planes and the fused decoders: (outs, descs, nbs).
+    shapes[k] is (F, H, W) or (H, W); outs[k], if given, a u8 tensor [F, H, W] or [H, W], possibly
+    a strided view; one of the two is needed, and both must agree.  var_nums[k], if given, is
+    sized for var_nbs[k] blocks (None: plane k's own).  devices[k]: where outs[k] is allocated."""
     import torch
     if shapes is None and outs is None:
         raise DctqError(f"{what} needs shapes or outs")
@@ -284,20 +367,17 @@ def _decode_outs(what, n, shapes, outs, var_nums, devices):
         if ts is not None and len(ts) != n:
             raise DctqError(f"{name} needs one entry per plane ({n}), got {len(ts)}")
     if shapes is not None:
-        shapes = [(1, *map(int, s)) if len(s) == 2 else tuple(map(int, s)) for s in shapes]
-        if any(len(s) != 3 for s in shapes):
-            raise DctqError("shapes entries must be (F, H, W) or (H, W)")
+        shapes = _shapes3(shapes)
     if outs is None:
         outs = [torch.empty(s, dtype=torch.uint8, device=d) for s, d in zip(shapes, devices)]
-    descs = (_Plane * n)(*[plane_desc(o) for o in outs])
-    nbs = [d.nframes * (d.width // 8) * (d.height // 8) for d in descs]
+    _, descs, nbs = _plane_set(outs)
     for k, (d, o) in enumerate(zip(descs, outs)):
         if shapes is not None and (d.nframes, d.height, d.width) != shapes[k]:
             raise DctqError(f"outs[{k}] is {tuple(o.shape)}, shapes[{k}] says {shapes[k]}")
         if d.width % 8 or d.height % 8:
             raise DctqError(f"outs[{k}]: width and height must be multiples of 8")
         if var_nums is not None:
-            _need(var_nums[k], nbs[k], torch.int32, f"var_nums[{k}]", o.device)
+            _need(var_nums[k], (var_nbs or nbs)[k], torch.int32, f"var_nums[{k}]", o.device)
     return outs, descs, nbs
 
 
@@ -371,6 +451,11 @@ class Plan:
     def _chk(self, rc: int) -> None:
         _check(rc, self._L)
 
+    def _fn(self, name: str):
+        """The entry point dctq_<name> of the plan's library, or its dctq_diag_<name> twin when a
+        variant is forced (only the twins honour it, csrc/dctq_diag.h)."""
+        return getattr(self._L, ("dctq_diag_" if self._diag else "dctq_") + name)
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.dctq_plan_destroy(self._h)
@@ -384,76 +469,56 @@ class Plan:
 
     def set_fallback_counter(self, counter):
         """counter: int64 CUDA tensor of one element (or None)."""
-        self._chk(self._L.dctq_plan_set_fallback_counter(self._h, C.c_void_p(counter.data_ptr()) if counter is not None else None))
+        self._chk(self._L.dctq_plan_set_fallback_counter(self._h, _ptr(counter)))
 
     # --- hot path -------------------------------------------------------
     def forward_quant(self, px, out=None, var_num=None, stream=None):
         """u8 [H,W] / [F,H,W] -> int16 [F*H/8*W/8, 64] quantized coefficients (bit-exact)."""
         import torch
         d = plane_desc(px)
-        nblk = d.nframes * (d.width // 8) * (d.height // 8)
-        if out is None:
-            out = torch.empty((nblk, 64), dtype=torch.int16, device=px.device)
-        _need(out, nblk * 64, torch.int16, "out", px.device)
+        nblk = _nblocks(d)
+        out = _out(out, (nblk, 64), torch.int16, px.device)
         if var_num is not None:
             _need(var_num, nblk, torch.int32, "var_num", px.device)
-        vn = C.c_void_p(var_num.data_ptr()) if var_num is not None else None
-        if self._diag:
-            op, vp = (C.c_void_p * 1)(out.data_ptr()), (C.c_void_p * 1)(vn.value) if vn is not None else None
-            self._chk(self._L.dctq_diag_forward_quant_planes(self._h, C.byref(d), 1, C.cast(op, C.c_void_p),
-                                                             C.cast(vp, C.c_void_p) if vp is not None else None,
-                                                             _stream_ptr(stream)))
+        if self._diag:   # a forced variant: the planes call has the twin, dctq_forward_quant has none
+            self.forward_quant_planes([px], [out], None if var_num is None else [var_num], stream)
         else:
-            self._chk(self._L.dctq_forward_quant(self._h, C.byref(d), C.c_void_p(out.data_ptr()), vn,
-                                                 _stream_ptr(stream)))
+            self._chk(self._L.dctq_forward_quant(self._h, C.byref(d), _ptr(out), _ptr(var_num), _stream_ptr(stream)))
         return out
 
     def forward_quant_planes(self, planes, outs=None, var_nums=None, stream=None):
         """Up to 4 u8 planes of any geometry (e.g. Y, Cb, Cr) in ONE launch; returns the list
         of int16 [nblk_k, 64] outputs, each equal to forward_quant(planes[k])."""
         import torch
-        n = len(planes)
-        descs = (_Plane * n)(*[plane_desc(px) for px in planes])
-        nbs = [d.nframes * (d.width // 8) * (d.height // 8) for d in descs]
-        if outs is None:
-            outs = [torch.empty((nb, 64), dtype=torch.int16, device=px.device) for nb, px in zip(nbs, planes)]
+        n, descs, nbs = _plane_set(planes)
+        outs = _per_plane(outs, nbs, 64, torch.int16, planes)
         _need_planes(outs, var_nums, None, nbs, planes)
-        cp = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
-        vp = (C.c_void_p * n)(*[v.data_ptr() for v in var_nums]) if var_nums is not None else None
-        fn = self._L.dctq_diag_forward_quant_planes if self._diag else self._L.dctq_forward_quant_planes
-        self._chk(fn(self._h, descs, n, C.cast(cp, C.c_void_p), C.cast(vp, C.c_void_p) if vp is not None else None,
-                     _stream_ptr(stream)))
+        self._chk(self._fn("forward_quant_planes")(self._h, descs, n, _ptrs(outs), _ptrs(var_nums), _stream_ptr(stream)))
         return outs
 
     def diag_movement_planes(self, planes, outs, stream=None, shape: int = 3, grid_mult: int = 0):
         """DIAGNOSTIC: the bytes forward_quant_planes moves, with no arithmetic (outs receive
         pixel bytes, not coefficients) -- the memory ceiling of that access pattern."""
-        n = len(planes)
-        descs = (_Plane * n)(*[plane_desc(px) for px in planes])
-        _need_planes(outs, None, None, [d.nframes * (d.width // 8) * (d.height // 8) for d in descs], planes)
-        cp = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
+        n, descs, nbs = _plane_set(planes)
+        _need_planes(outs, None, None, nbs, planes)
         if self._L is not _diag:
             raise DctqError("diag_movement_planes needs a plan of the diagnostic library (Plan(..., diagnostic=True))")
         if grid_mult:
-            self._chk(self._L.dctq_diag_movement_grid_planes(self._h, descs, n, C.cast(cp, C.c_void_p), grid_mult,
+            self._chk(self._L.dctq_diag_movement_grid_planes(self._h, descs, n, _ptrs(outs), grid_mult,
                                                              _stream_ptr(stream)))
             return outs
         fn = self._L.dctq_diag_movement_planes if shape == 3 else self._L.dctq_diag_movement_v2_planes
-        self._chk(fn(self._h, descs, n, C.cast(cp, C.c_void_p), _stream_ptr(stream)))
+        self._chk(fn(self._h, descs, n, _ptrs(outs), _stream_ptr(stream)))
         return outs
 
     def diag_rt_movement_planes(self, planes, outs, recons, stream=None):
         """DIAGNOSTIC: the bytes round_trip_planes moves (its grid, stage and stores), with no
         arithmetic (outs/recons receive pixel bytes) -- the memory ceiling of that pattern."""
-        n = len(planes)
-        descs = (_Plane * n)(*[plane_desc(px) for px in planes])
-        nbs = [d.nframes * (d.width // 8) * (d.height // 8) for d in descs]
+        n, descs, nbs = _plane_set(planes)
         _need_planes(outs, None, recons, nbs, planes)
         if self._L is not _diag:
             raise DctqError("diag_rt_movement_planes needs a plan of the diagnostic library (Plan(..., diagnostic=True))")
-        cp = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
-        rp = (C.c_void_p * n)(*[r.data_ptr() for r in recons])
-        self._chk(self._L.dctq_diag_rt_movement_planes(self._h, descs, n, C.cast(cp, C.c_void_p), C.cast(rp, C.c_void_p),
+        self._chk(self._L.dctq_diag_rt_movement_planes(self._h, descs, n, _ptrs(outs), _ptrs(recons),
                                                       _stream_ptr(stream)))
         return outs, recons
 
@@ -462,20 +527,12 @@ class Plan:
         int16 [nblk_k, 64] (== forward_quant) and float32 [nblk_k, 64]
         (== inverse(coef, var_num) within 1e-4)."""
         import torch
-        n = len(planes)
-        descs = (_Plane * n)(*[plane_desc(px) for px in planes])
-        nbs = [d.nframes * (d.width // 8) * (d.height // 8) for d in descs]
-        if outs is None:
-            outs = [torch.empty((nb, 64), dtype=torch.int16, device=px.device) for nb, px in zip(nbs, planes)]
-        if recons is None:
-            recons = [torch.empty((nb, 64), dtype=torch.float32, device=px.device) for nb, px in zip(nbs, planes)]
+        n, descs, nbs = _plane_set(planes)
+        outs = _per_plane(outs, nbs, 64, torch.int16, planes)
+        recons = _per_plane(recons, nbs, 64, torch.float32, planes)
         _need_planes(outs, var_nums, recons, nbs, planes)
-        cp = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
-        rp = (C.c_void_p * n)(*[r.data_ptr() for r in recons])
-        vp = (C.c_void_p * n)(*[v.data_ptr() for v in var_nums]) if var_nums is not None else None
-        self._chk(self._L.dctq_round_trip_planes(self._h, descs, n, C.cast(cp, C.c_void_p),
-                                            C.cast(vp, C.c_void_p) if vp is not None else None,
-                                            C.cast(rp, C.c_void_p), _stream_ptr(stream)))
+        self._chk(self._L.dctq_round_trip_planes(self._h, descs, n, _ptrs(outs), _ptrs(var_nums), _ptrs(recons),
+                                                 _stream_ptr(stream)))
         return outs, recons
 
     @property
@@ -497,39 +554,34 @@ class Plan:
         sb = self.symbol_bytes if symbol_bytes is None else int(symbol_bytes)
         if sb not in (2, 4):
             raise ValueError("symbol_bytes must be 2 or 4")
-        n = len(planes)
-        descs = (_Plane * n)(*[plane_desc(px) for px in planes])
-        nbs = [d.nframes * (d.width // 8) * (d.height // 8) for d in descs]
+        n, descs, nbs = _plane_set(planes)
         nb = sum(nbs)
         dev = planes[0].device
-        if outs is None:
-            outs = [torch.empty((m, 64), dtype=torch.int16, device=dev) for m in nbs]
+        outs = _per_plane(outs, nbs, 64, torch.int16, planes, device=dev)
         _need_planes(outs, None, None, nbs, planes)
         cap = 64 * nb if capacity is None else int(capacity)
         off = torch.empty(nb + 1, dtype=torch.int32, device=dev)
         sym = torch.empty(max(cap, 1), dtype=torch.int16 if sb == 2 else torch.int32, device=dev)
-        ws = torch.empty(int(self._L.dctq_encode_workspace_bytes(nb)) // 4 + 1, dtype=torch.int32, device=dev)
-        cp = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
+        ws = _workspace(self._L.dctq_encode_workspace_bytes, nb, dev)
         fn = self._L.dctq_encode_planes16 if sb == 2 else self._L.dctq_encode_planes
-        self._chk(fn(self._h, descs, n, C.cast(cp, C.c_void_p), C.c_void_p(off.data_ptr()),
-                     C.c_void_p(sym.data_ptr()), cap, C.c_void_p(ws.data_ptr()), _stream_ptr(stream)))
-        total = int(off[nb].item()) & 0xFFFFFFFF
+        self._chk(fn(self._h, descs, n, _ptrs(outs), _ptr(off), _ptr(sym), cap, _ptr(ws), _stream_ptr(stream)))
+        total = _read_back(off[nb:], stream)[0]
         return outs, off, sym[:min(total, cap)]
+
+    def _per_block_planes(self, fn, planes, out, stream):
+        """The body of huffman_bits_planes and distortion_planes: one int32 per block of up to 4
+        planes, blocks numbered plane by plane."""
+        import torch
+        n, descs, nbs = _plane_set(planes)
+        out = _out(out, (sum(nbs),), torch.int32, planes[0].device)
+        self._chk(fn(self._h, descs, n, _ptr(out), _stream_ptr(stream)))
+        return out
 
     def huffman_bits_planes(self, planes, out=None, stream=None):
         """Per-block Huffman size straight from up to 4 u8 planes (the whole per-block loop of
         tests/test_entropy.c:300-341 on the GPU, coefficients kept on chip): int32 [N], blocks
         numbered plane by plane, equal to huffman_bits(cat(forward_quant_planes(planes)))."""
-        import torch
-        n = len(planes)
-        descs = (_Plane * n)(*[plane_desc(px) for px in planes])
-        nb = sum(d.nframes * (d.width // 8) * (d.height // 8) for d in descs)
-        if out is None:
-            out = torch.empty(nb, dtype=torch.int32, device=planes[0].device)
-        _need(out, nb, torch.int32, "out", planes[0].device)
-        self._chk(self._L.dctq_huffman_bits_planes(self._h, descs, n, C.c_void_p(out.data_ptr()),
-                                                   _stream_ptr(stream)))
-        return out
+        return self._per_block_planes(self._L.dctq_huffman_bits_planes, planes, out, stream)
 
     def distortion_planes(self, planes, out=None, stream=None):
         """Per-block squared error of the decoded picture straight from up to 4 u8 planes in ONE
@@ -537,18 +589,9 @@ class Plan:
         blocks numbered as huffman_bits_planes numbers them, entry b the sum over block b of
         (px - dec)^2 with dec bit for bit the pixels of
         decode_planes(forward_quant_planes(planes, var_nums), var_nums)."""
-        import torch
-        n = len(planes)
-        if n == 0:
+        if len(planes) == 0:
             raise DctqError("distortion_planes needs at least one plane")
-        descs = (_Plane * n)(*[plane_desc(px) for px in planes])
-        nb = sum(d.nframes * (d.width // 8) * (d.height // 8) for d in descs)
-        if out is None:
-            out = torch.empty(nb, dtype=torch.int32, device=planes[0].device)
-        _need(out, nb, torch.int32, "out", planes[0].device)
-        self._chk(self._L.dctq_distortion_planes(self._h, descs, n, C.c_void_p(out.data_ptr()),
-                                                 _stream_ptr(stream)))
-        return out
+        return self._per_block_planes(self._L.dctq_distortion_planes, planes, out, stream)
 
     def rate_distortion_planes(self, planes, stream=None):
         """(bits, sse) = (huffman_bits_planes(planes), distortion_planes(planes)): both columns
@@ -559,12 +602,9 @@ class Plan:
     def forward_float(self, px, out=None, stream=None):
         import torch
         d = plane_desc(px)
-        nblk = d.nframes * (d.width // 8) * (d.height // 8)
-        if out is None:
-            out = torch.empty((nblk, 64), dtype=torch.float32, device=px.device)
-        _need(out, nblk * 64, torch.float32, "out", px.device)
-        fn = self._L.dctq_diag_forward_float if self._diag else self._L.dctq_forward_float
-        self._chk(fn(self._h, C.byref(d), C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+        nblk = _nblocks(d)
+        out = _out(out, (nblk, 64), torch.float32, px.device)
+        self._chk(self._fn("forward_float")(self._h, C.byref(d), _ptr(out), _stream_ptr(stream)))
         return out
 
     def inverse(self, coef, var_num=None, out=None, stream=None):
@@ -574,14 +614,10 @@ class Plan:
         import torch
         _need(coef, 0, torch.int16, "coef")
         n = coef.numel() // 64
-        if out is None:
-            out = torch.empty((n, 64), dtype=torch.float32, device=coef.device)
-        _need(out, n * 64, torch.float32, "out", coef.device)
+        out = _out(out, (n, 64), torch.float32, coef.device)
         if var_num is not None:
             _need(var_num, n, torch.int32, "var_num", coef.device)
-        fn = self._L.dctq_diag_inverse if self._diag else self._L.dctq_inverse
-        self._chk(fn(self._h, C.c_void_p(coef.data_ptr()), C.c_void_p(var_num.data_ptr()) if var_num is not None else None,
-                     n, C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+        self._chk(self._fn("inverse")(self._h, _ptr(coef), _ptr(var_num), n, _ptr(out), _stream_ptr(stream)))
         return out
 
     def decode_planes(self, coefs, shapes=None, outs=None, var_nums=None, stream=None):
@@ -600,14 +636,25 @@ class Plan:
         import torch
         outs, descs, nbs = _decode_outs("decode_planes", len(coefs), shapes, outs, var_nums,
                                         [c.device for c in coefs])
-        n = len(coefs)
         for k, (o, c) in enumerate(zip(outs, coefs)):
             _need(c, nbs[k] * 64, torch.int16, f"coefs[{k}]", o.device)
-        cp = (C.c_void_p * n)(*[c.data_ptr() for c in coefs])
-        vp = (C.c_void_p * n)(*[v.data_ptr() for v in var_nums]) if var_nums is not None else None
-        self._chk(self._L.dctq_decode_planes(self._h, C.cast(cp, C.c_void_p),
-                                             C.cast(vp, C.c_void_p) if vp is not None else None, descs, n,
+        self._chk(self._L.dctq_decode_planes(self._h, _ptrs(coefs), _ptrs(var_nums), descs, len(coefs),
                                              _stream_ptr(stream)))
+        return outs
+
+    def _decode_stream(self, what, need, src, offsets, shapes, outs, var_nums, stream, launch, stored=None):
+        """The body of the fused decoders decode_symbols, decode_bits and decode_bits_window (what):
+        the source checked by its validator (need: _need_symbols or _need_bytes), the destinations
+        made or checked (_decode_outs), the offsets checked, all on one device, then the wrapper's
+        own C call, launch(var_nums, descs, n, stream).  stored: the block counts the stream is
+        numbered over and var_nums are sized by, where they are not the destinations' own (a window)."""
+        need(src)
+        n = len(shapes if shapes is not None else outs if outs is not None else ())
+        outs, descs, nbs = _decode_outs(what, n, shapes, outs, var_nums, [src.device] * n, stored)
+        _need_byte_offsets(offsets, sum(stored or nbs), src)
+        if any(o.device != src.device for o in outs):
+            raise DctqError(f"{'symbols' if need is _need_symbols else 'bytes'}, offsets and outs must be on one device")
+        self._chk(launch(_ptrs(var_nums), descs, n, _stream_ptr(stream)))
         return outs
 
     def decode_symbols(self, symbols, offsets, shapes=None, outs=None, var_nums=None, stream=None):
@@ -619,25 +666,10 @@ class Plan:
         whatever the plan's own symbol_bytes.  shapes / outs / var_nums as decode_planes,
         and its error bound for the domain the symbols' values fall in (a 4-byte symbol
         carries any int16, a 2-byte symbol [-512, 511])."""
-        import torch
-        if not isinstance(symbols, torch.Tensor) or not symbols.is_cuda or symbols.dtype not in (torch.int16, torch.int32):
-            raise DctqError("symbols must be an int16 or int32 tensor on a HIP device")
-        if not symbols.is_contiguous():
-            raise DctqError("symbols must be contiguous")
-        n = len(shapes if shapes is not None else outs if outs is not None else ())
-        outs, descs, nbs = _decode_outs("decode_symbols", n, shapes, outs, var_nums, [symbols.device] * n)
-        if (not isinstance(offsets, torch.Tensor) or not offsets.is_cuda or offsets.dtype != torch.int32
-                or not offsets.is_contiguous() or offsets.numel() != sum(nbs) + 1):
-            raise DctqError(f"offsets must be a contiguous int32 device tensor of {sum(nbs) + 1} elements "
-                            "(one per block of every plane, plus one)")
-        if offsets.device != symbols.device or any(o.device != symbols.device for o in outs):
-            raise DctqError("symbols, offsets and outs must be on one device")
-        vp = (C.c_void_p * n)(*[v.data_ptr() for v in var_nums]) if var_nums is not None else None
-        self._chk(self._L.dctq_decode_symbols_planes(
-            self._h, C.c_void_p(symbols.data_ptr()), 2 if symbols.dtype == torch.int16 else 4,
-            C.c_void_p(offsets.data_ptr()), C.cast(vp, C.c_void_p) if vp is not None else None, descs, n,
-            _stream_ptr(stream)))
-        return outs
+        return self._decode_stream(
+            "decode_symbols", _need_symbols, symbols, offsets, shapes, outs, var_nums, stream,
+            lambda vn, descs, n, s: self._L.dctq_decode_symbols_planes(
+                self._h, _ptr(symbols), symbols.element_size(), _ptr(offsets), vn, descs, n, s))
 
     def decode_bits(self, bytes, offsets, shapes=None, outs=None, var_nums=None, stream=None):
         """The bit-packed stream "bits v1" -> u8 pixels of up to 4 planes in ONE launch, with no
@@ -646,21 +678,9 @@ class Plan:
         [sum(nblk_k) + 1], byte offsets) as bits_pack returns them, blocks numbered plane by
         plane; any bytes decode.  shapes / outs / var_nums as decode_planes, and its error bound
         for the domain the decoded values fall in (a packed symbol carries any int16)."""
-        import torch
-        if not isinstance(bytes, torch.Tensor) or not bytes.is_cuda or bytes.dtype != torch.uint8:
-            raise DctqError("bytes must be a uint8 tensor on a HIP device")
-        if not bytes.is_contiguous():
-            raise DctqError("bytes must be contiguous")
-        n = len(shapes if shapes is not None else outs if outs is not None else ())
-        outs, descs, nbs = _decode_outs("decode_bits", n, shapes, outs, var_nums, [bytes.device] * n)
-        _need_byte_offsets(offsets, sum(nbs), bytes)
-        if any(o.device != bytes.device for o in outs):
-            raise DctqError("bytes, offsets and outs must be on one device")
-        vp = (C.c_void_p * n)(*[v.data_ptr() for v in var_nums]) if var_nums is not None else None
-        self._chk(self._L.dctq_decode_bits_planes(
-            self._h, C.c_void_p(bytes.data_ptr()), C.c_void_p(offsets.data_ptr()),
-            C.cast(vp, C.c_void_p) if vp is not None else None, descs, n, _stream_ptr(stream)))
-        return outs
+        return self._decode_stream(
+            "decode_bits", _need_bytes, bytes, offsets, shapes, outs, var_nums, stream,
+            lambda vn, descs, n, s: self._L.dctq_decode_bits_planes(self._h, _ptr(bytes), _ptr(offsets), vn, descs, n, s))
 
     def decode_bits_window(self, bytes, offsets, shapes, windows, outs=None, var_nums=None, stream=None):
         """A window of every plane of a "bits v1" stream -> u8 pixels in ONE launch that reads
@@ -673,24 +693,17 @@ class Plan:
         (bytes outside them are not touched); var_nums[k] (adaptive plans) is the whole stored
         plane's.  The work unit is a run of up to 64 blocks of one window row
         (tools/window_ref.py): a window narrower than 512 pixels leaves part of each wave idle."""
-        import torch
-        if not isinstance(bytes, torch.Tensor) or not bytes.is_cuda or bytes.dtype != torch.uint8:
-            raise DctqError("bytes must be a uint8 tensor on a HIP device")
-        if not bytes.is_contiguous():
-            raise DctqError("bytes must be contiguous")
         n = len(shapes)
         if len(windows) != n:
             raise DctqError(f"windows needs one entry per plane ({n}), got {len(windows)}")
-        shapes = [(1, *map(int, s)) if len(s) == 2 else tuple(map(int, s)) for s in shapes]
-        if any(len(s) != 3 for s in shapes):
-            raise DctqError("shapes entries must be (F, H, W) or (H, W)")
+        shapes = _shapes3(shapes)
         wins, wshapes = [], []
         for k, ((f, h, w), win) in enumerate(zip(shapes, windows)):
             try:
                 (f0, f1), (y0, y1), (x0, x1) = [tuple(map(int, r)) for r in win]
             except (TypeError, ValueError):
                 raise DctqError(f"windows[{k}] must be ((f0, f1), (y0, y1), (x0, x1))") from None
-            if f < 1 or h < 8 or w < 8 or h % 8 or w % 8:
+            if not _whole_blocks(f, h, w):
                 raise DctqError(f"shapes[{k}] {(f, h, w)}: height and width must be multiples of 8, nframes >= 1")
             if not (0 <= f0 < f1 <= f and 0 <= y0 < y1 <= h and 0 <= x0 < x1 <= w):
                 raise DctqError(f"windows[{k}] {win} is empty or leaves the stored plane {(f, h, w)}")
@@ -698,25 +711,17 @@ class Plan:
                 raise DctqError(f"windows[{k}] {win}: rows and columns must be multiples of 8")
             wins.append(_Window(w, h, f, x0, y0, f0))
             wshapes.append((f1 - f0, y1 - y0, x1 - x0))
-        nbs = [f * (h // 8) * (w // 8) for f, h, w in shapes]
+        nbs = [_nblocks(s) for s in shapes]
         if sum(nbs) >= 1 << 26:
             raise DctqError("more than 2^26 - 1 blocks in one decode")
-        outs, descs, _ = _decode_outs("decode_bits_window", n, wshapes, outs, None, [bytes.device] * n)
-        _need_byte_offsets(offsets, sum(nbs), bytes)
-        if any(o.device != bytes.device for o in outs):
-            raise DctqError("bytes, offsets and outs must be on one device")
         if self.adaptive and var_nums is None:
             raise DctqError("adaptive decode needs var_nums")
-        if var_nums is not None:
-            if len(var_nums) != n:
-                raise DctqError(f"var_nums needs one entry per plane ({n}), got {len(var_nums)}")
-            for k, v in enumerate(var_nums):
-                _need(v, nbs[k], torch.int32, f"var_nums[{k}]", bytes.device)
-        vp = (C.c_void_p * n)(*[v.data_ptr() for v in var_nums]) if var_nums is not None else None
-        self._chk(self._L.dctq_decode_bits_window_planes(
-            self._h, C.c_void_p(bytes.data_ptr()), C.c_void_p(offsets.data_ptr()),
-            C.cast(vp, C.c_void_p) if vp is not None else None, (_Window * n)(*wins), descs, n, _stream_ptr(stream)))
-        return outs
+        wins = (_Window * n)(*wins)
+        return self._decode_stream(
+            "decode_bits_window", _need_bytes, bytes, offsets, wshapes, outs, var_nums, stream,
+            lambda vn, descs, n, s: self._L.dctq_decode_bits_window_planes(
+                self._h, _ptr(bytes), _ptr(offsets), vn, wins, descs, n, s),
+            stored=nbs)
 
     def encode_bits_planes(self, planes, outs=None, capacity=None, stream=None, symbol_bytes=None):
         """encode_planes + bits_pack: forward, zigzag/RLE and the bit-packed stream of up to 4
@@ -751,15 +756,13 @@ def rle_encode(coef, stream=None):
     import torch
     _need(coef, 0, torch.int16, "coef")
     n = coef.numel() // 64
-    ws = torch.empty(int(lib().dctq_rle_workspace_bytes(n)) // 4 + 1, dtype=torch.int32, device=coef.device)
+    ws = _workspace(lib().dctq_rle_workspace_bytes, n, coef.device)
     off = torch.empty(n + 1, dtype=torch.int32, device=coef.device)
     s = _stream_ptr(stream)
-    _check(lib().dctq_rle_count(C.c_void_p(coef.data_ptr()), n, C.c_void_p(off.data_ptr()),
-                                C.c_void_p(ws.data_ptr()), s))
-    total = int(off[n].item()) & 0xFFFFFFFF
+    _check(lib().dctq_rle_count(_ptr(coef), n, _ptr(off), _ptr(ws), s))
+    total = _read_back(off[n:], stream)[0]
     sym = torch.empty(max(total, 1), dtype=torch.int32, device=coef.device)
-    _check(lib().dctq_rle_emit(C.c_void_p(coef.data_ptr()), n, C.c_void_p(off.data_ptr()),
-                               C.c_void_p(sym.data_ptr()), s))
+    _check(lib().dctq_rle_emit(_ptr(coef), n, _ptr(off), _ptr(sym), s))
     return off, sym[:total]
 
 
@@ -770,10 +773,8 @@ def huffman_bits(coef, out=None, stream=None):
     import torch
     _need(coef, 0, torch.int16, "coef")
     n = coef.numel() // 64
-    if out is None:
-        out = torch.empty(n, dtype=torch.int32, device=coef.device)
-    _need(out, n, torch.int32, "out", coef.device)
-    _check(lib().dctq_huffman_bits(C.c_void_p(coef.data_ptr()), n, C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+    out = _out(out, (n,), torch.int32, coef.device)
+    _check(lib().dctq_huffman_bits(_ptr(coef), n, _ptr(out), _stream_ptr(stream)))
     return out
 
 
@@ -793,13 +794,30 @@ def rle_decode(symbols, offsets, out=None, stream=None):
     zigzag_to_block).  int16 symbols are the 2-byte format (dctq_rle_decode16)."""
     import torch
     n = offsets.numel() - 1
-    if out is None:
-        out = torch.empty((n, 64), dtype=torch.int16, device=offsets.device)
-    _need(out, n * 64, torch.int16, "out", offsets.device)
+    out = _out(out, (n, 64), torch.int16, offsets.device)
     fn = lib().dctq_rle_decode16 if symbols.dtype == torch.int16 else lib().dctq_rle_decode
-    _check(fn(C.c_void_p(symbols.data_ptr()), C.c_void_p(offsets.data_ptr()), n, C.c_void_p(out.data_ptr()),
-              _stream_ptr(stream)))
+    _check(fn(_ptr(symbols), _ptr(offsets), n, _ptr(out), _stream_ptr(stream)))
     return out
+
+
+def _need_symbols(symbols) -> int:
+    """The symbols of a run-length stream: a contiguous int16 or int32 device tensor.  Returns
+    the symbol format its dtype picks (2 or 4 bytes)."""
+    import torch
+    if not isinstance(symbols, torch.Tensor) or not symbols.is_cuda or symbols.dtype not in (torch.int16, torch.int32):
+        raise DctqError("symbols must be an int16 or int32 tensor on a HIP device")
+    if not symbols.is_contiguous():
+        raise DctqError("symbols must be contiguous")
+    return 2 if symbols.dtype == torch.int16 else 4
+
+
+def _need_bytes(bytes) -> None:
+    """The bytes of a packed stream: a contiguous uint8 device tensor."""
+    import torch
+    if not isinstance(bytes, torch.Tensor) or not bytes.is_cuda or bytes.dtype != torch.uint8:
+        raise DctqError("bytes must be a uint8 tensor on a HIP device")
+    if not bytes.is_contiguous():
+        raise DctqError("bytes must be contiguous")
 
 
 def _need_byte_offsets(offsets, nblk, bytes):
@@ -823,13 +841,9 @@ def bits_pack(symbols, offsets, symbol_bytes=None, capacity=None, stream=None):
     (int16: 2-byte, int32: 4-byte), and symbol_bytes, if given, must agree.  Returns
     (bytes uint8 [min(total, capacity)], byte_offsets int32 [N+1], uint32 bit patterns,
     always complete).  capacity None: two passes, the second sized by the first's total;
-    0: the offsets only.  Reads the total back (one sync)."""
+    0: the offsets only.  Reads the total back (one sync a pass)."""
     import torch
-    if not isinstance(symbols, torch.Tensor) or not symbols.is_cuda or symbols.dtype not in (torch.int16, torch.int32):
-        raise DctqError("symbols must be an int16 or int32 tensor on a HIP device")
-    if not symbols.is_contiguous():
-        raise DctqError("symbols must be contiguous")
-    sb = 2 if symbols.dtype == torch.int16 else 4
+    sb = _need_symbols(symbols)
     if symbol_bytes is not None and int(symbol_bytes) != sb:
         raise DctqError(f"symbol_bytes {symbol_bytes} does not match symbols of {symbols.dtype}")
     _need_byte_offsets(offsets, None, symbols)
@@ -838,17 +852,13 @@ def bits_pack(symbols, offsets, symbol_bytes=None, capacity=None, stream=None):
     n = offsets.numel() - 1
     dev = symbols.device
     L = lib()
-    ws = torch.empty(int(L.dctq_bits_workspace_bytes(n)) // 4 + 1, dtype=torch.int32, device=dev)
+    ws = _workspace(L.dctq_bits_workspace_bytes, n, dev)
     boff = torch.empty(n + 1, dtype=torch.int32, device=dev)
     s = _stream_ptr(stream)
 
     def run(buf, cap):
-        _check(L.dctq_bits_pack(C.c_void_p(symbols.data_ptr()), sb, C.c_void_p(offsets.data_ptr()), n,
-                                C.c_void_p(boff.data_ptr()), C.c_void_p(buf.data_ptr()) if buf is not None else None,
-                                cap, C.c_void_p(ws.data_ptr()), s))
-        if stream is not None:
-            stream.synchronize()
-        return int(boff[n].item()) & 0xFFFFFFFF
+        _check(L.dctq_bits_pack(_ptr(symbols), sb, _ptr(offsets), n, _ptr(boff), _ptr(buf), cap, _ptr(ws), s))
+        return _read_back(boff[n:], stream)[0]
 
     cap = run(None, 0) if capacity is None else int(capacity)  # offsets only: the total
     out = torch.empty(max(cap, 4), dtype=torch.uint8, device=dev)
@@ -860,17 +870,11 @@ def bits_decode(bytes, offsets, out=None, stream=None):
     """Inverse of bits_pack, counterpart of rle_decode: int16 [N, 64] blocks from the packed
     stream (dctq_bits_decode).  Any bytes decode."""
     import torch
-    if not isinstance(bytes, torch.Tensor) or not bytes.is_cuda or bytes.dtype != torch.uint8:
-        raise DctqError("bytes must be a uint8 tensor on a HIP device")
-    if not bytes.is_contiguous():
-        raise DctqError("bytes must be contiguous")
+    _need_bytes(bytes)
     _need_byte_offsets(offsets, None, bytes)
     n = offsets.numel() - 1
-    if out is None:
-        out = torch.empty((n, 64), dtype=torch.int16, device=bytes.device)
-    _need(out, n * 64, torch.int16, "out", bytes.device)
-    _check(lib().dctq_bits_decode(C.c_void_p(bytes.data_ptr()), C.c_void_p(offsets.data_ptr()), n,
-                                  C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+    out = _out(out, (n, 64), torch.int16, bytes.device)
+    _check(lib().dctq_bits_decode(_ptr(bytes), _ptr(offsets), n, _ptr(out), _stream_ptr(stream)))
     return out
 
 
@@ -1031,19 +1035,6 @@ def _align16(n: int) -> int:
     return (n + 15) // 16 * 16
 
 
-def _on_stream(stream):
-    """torch's own copies and fills go to `stream` too (None: the current one)."""
-    import contextlib
-    import torch
-    return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
-
-
-def _read_back(t, stream):
-    """A small device tensor as a list of ints (one sync, of `stream` when given)."""
-    with _on_stream(stream):
-        return t.cpu().tolist()
-
-
 def block_lengths(offsets, length_bytes=None, stream=None):
     """Byte offsets int32 [N+1] (uint32 bit patterns, as bits_pack returns them) -> (lengths,
     length_bytes): lengths[b] = offsets[b+1] - offsets[b] as uint8 [N] (length_bytes 1) or int16
@@ -1059,9 +1050,8 @@ def block_lengths(offsets, length_bytes=None, stream=None):
     mx = torch.empty(1, dtype=torch.int32, device=offsets.device)
     for lb in ((1, 2) if length_bytes is None else (int(length_bytes),)):
         out = torch.empty(n, dtype=torch.uint8 if lb == 1 else torch.int16, device=offsets.device)
-        _check(lib().dctq_block_lengths(C.c_void_p(offsets.data_ptr()), n, lb, C.c_void_p(out.data_ptr()),
-                                        C.c_void_p(mx.data_ptr()), _stream_ptr(stream)))
-        longest = _read_back(mx, stream)[0] & 0xFFFFFFFF
+        _check(lib().dctq_block_lengths(_ptr(offsets), n, lb, _ptr(out), _ptr(mx), _stream_ptr(stream)))
+        longest = _read_back(mx, stream)[0]
         if longest < 1 << (8 * lb):
             return out, lb
     raise DctqError(f"a block of {longest} bytes does not fit length_bytes {lb}")
@@ -1078,13 +1068,11 @@ def block_offsets(lengths, out=None, stream=None):
     if not lengths.is_contiguous() or lengths.numel() < 1:
         raise DctqError("lengths must be contiguous and hold at least one block")
     n = lengths.numel()
-    if out is None:
-        out = torch.empty(n + 1, dtype=torch.int32, device=lengths.device)
-    _need(out, n + 1, torch.int32, "out", lengths.device)
+    out = _out(out, (n + 1,), torch.int32, lengths.device)
     L = lib()
-    ws = torch.empty(int(L.dctq_block_offsets_workspace_bytes(n)) // 4 + 1, dtype=torch.int32, device=lengths.device)
-    _check(L.dctq_block_offsets(C.c_void_p(lengths.data_ptr()), 1 if lengths.dtype == torch.uint8 else 2, n,
-                                C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), _stream_ptr(stream)))
+    ws = _workspace(L.dctq_block_offsets_workspace_bytes, n, lengths.device)
+    _check(L.dctq_block_offsets(_ptr(lengths), 1 if lengths.dtype == torch.uint8 else 2, n, _ptr(out), _ptr(ws),
+                                _stream_ptr(stream)))
     return out
 
 
@@ -1094,9 +1082,9 @@ def _frame_geometry(shapes, colour) -> int:
         raise DctqError("frame: nplanes must be 1..4")
     n = 0
     for f, h, w in shapes:
-        if w < 8 or h < 8 or w % 8 or h % 8 or f < 1:
+        if not _whole_blocks(f, h, w):
             raise DctqError(f"frame: plane {w} x {h} x {f}: width and height must be multiples of 8, nframes >= 1")
-        n += f * (h // 8) * (w // 8)
+        n += _nblocks((f, h, w))
     if not 1 <= n <= _FRAME_MAX_BLOCKS:
         raise DctqError(f"frame: nblocks {n} outside 1..{_FRAME_MAX_BLOCKS}")
     if colour:
@@ -1190,18 +1178,13 @@ def frame_pack(bytes, offsets, shapes, quality, adaptive=False, var_nums=None, c
     it is frame v1, byte for byte."""
     import struct
     import torch
-    if not isinstance(bytes, torch.Tensor) or not bytes.is_cuda or bytes.dtype != torch.uint8 or not bytes.is_contiguous():
-        raise DctqError("bytes must be a contiguous uint8 tensor on a HIP device")
-    shapes = [(1, *map(int, s)) if len(s) == 2 else tuple(map(int, s)) for s in shapes]
-    if any(len(s) != 3 for s in shapes):
-        raise DctqError("shapes entries must be (F, H, W) or (H, W)")
+    _need_bytes(bytes)
+    shapes = _shapes3(shapes)
     nblocks = _frame_geometry(shapes, colour)
     if crops is not None:
         crops = [(int(pb), int(pr)) for pb, pr in crops]
-        if len(crops) != len(shapes):
-            raise DctqError("frame: crops needs one (pad_bottom, pad_right) per plane")
-        if any(pb or pr for pb, pr in crops):
-            _frame_crops(crops, shapes, colour)
+        if len(crops) != len(shapes) or any(pb or pr for pb, pr in crops):
+            _frame_crops(crops, shapes, colour)   # which refuses a wrong count first
         else:
             crops = None
     _need_byte_offsets(offsets, nblocks, bytes)
@@ -1209,7 +1192,7 @@ def frame_pack(bytes, offsets, shapes, quality, adaptive=False, var_nums=None, c
     sections = []
     lengths, lb = block_lengths(offsets, stream=stream)
     sections.append(lengths.view(torch.uint8))
-    first, total = (v & 0xFFFFFFFF for v in _read_back(offsets[[0, nblocks]], stream))
+    first, total = _read_back(offsets[[0, nblocks]], stream)
     if first != 0 or total != bytes.numel():
         raise DctqError(f"offsets run from {first} to {total}, bytes holds {bytes.numel()}")
     if adaptive:
@@ -1221,7 +1204,7 @@ def frame_pack(bytes, offsets, shapes, quality, adaptive=False, var_nums=None, c
     header_bytes = 48 + 16 * len(shapes)
     starts, end = _frame_sections(header_bytes, nblocks, lb, bool(adaptive), bytes.numel())
     head = bytearray(FRAME_MAGIC if crops is None else FRAME_MAGIC_CROP)
-    head += struct.pack("<IBBBBB7xQQQ", header_bytes, min(max(int(quality), 1), 100), int(bool(adaptive)), len(shapes),
+    head += struct.pack("<IBBBBB7xQQQ", header_bytes, _clamp_quality(quality), int(bool(adaptive)), len(shapes),
                         lb, int(bool(colour)), nblocks, bytes.numel(), end)
     for (f, h, w), (pb, pr) in zip(shapes, crops or [(0, 0)] * len(shapes)):
         head += struct.pack("<IIII", w, h, f, pr | pb << 16)
@@ -1266,14 +1249,13 @@ def frame_unpack(buf, stream=None) -> dict:
     n, lb, starts = h["nblocks"], h["length_bytes"], h["starts"]
     lengths = buf[starts[0]:starts[0] + n * lb]
     offsets = block_offsets(lengths if lb == 1 else lengths.view(torch.int16), stream=stream)
-    total = _read_back(offsets[n:], stream)[0] & 0xFFFFFFFF
+    total = _read_back(offsets[n:], stream)[0]
     if total != h["payload_bytes"]:
         raise DctqError(f"frame: the lengths sum to {total}, payload_bytes says {h['payload_bytes']}")
     var_nums = None
     if h["adaptive"]:
         vn = buf[starts[1]:starts[1] + 4 * n].view(torch.int32)
-        nbs = [f * (hh // 8) * (w // 8) for f, hh, w in h["shapes"]]
-        var_nums = list(torch.split(vn, nbs))
+        var_nums = list(torch.split(vn, [_nblocks(s) for s in h["shapes"]]))
     return {"quality": h["quality"], "adaptive": h["adaptive"], "colour": h["colour"], "shapes": h["shapes"],
             "length_bytes": lb, "offsets": offsets, "bytes": buf[starts[-1]:starts[-1] + h["payload_bytes"]],
             "var_nums": var_nums, "crops": h["crops"]}
@@ -1285,7 +1267,7 @@ _frame_plans = {}
 def _frame_plan(quality: int, adaptive: bool, device) -> "Plan":
     """compress / decompress keep one Plan per (quality, adaptive, device) and library (grid_limit)."""
     import torch
-    key = (min(max(int(quality), 1), 100), bool(adaptive), torch.device(device).index or 0, _grid_limited)
+    key = (_clamp_quality(quality), bool(adaptive), torch.device(device).index or 0, _grid_limited)
     if key not in _frame_plans:
         with torch.cuda.device(key[2]):
             _frame_plans[key] = Plan(key[0], key[1])
@@ -1323,7 +1305,7 @@ def compress(src, quality: int = 50, adaptive: bool = False, subsampling: str = 
     plan = _frame_plan(quality, adaptive, planes[0].device)
     var_nums = None
     if adaptive:
-        nbs = [f * (h // 8) * (w // 8) for f, h, w in shapes]
+        nbs = [_nblocks(s) for s in shapes]
         coef = torch.empty((sum(nbs), 64), dtype=torch.int16, device=planes[0].device)
         var_nums = torch.empty(sum(nbs), dtype=torch.int32, device=planes[0].device)
         plan.forward_quant_planes(planes, outs=list(torch.split(coef, nbs)), var_nums=list(torch.split(var_nums, nbs)),
