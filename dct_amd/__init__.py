@@ -110,6 +110,7 @@ def _bind(L: C.CDLL, diagnostic: bool) -> C.CDLL:
         "dctq_bits_decode": ([vp, vp, ll, vp, vp], i),
         "dctq_decode_bits_planes": ([vp, vp, vp, vp, C.POINTER(_Plane), i, vp], i),
         "dctq_decode_bits_window_planes": ([vp, vp, vp, vp, C.POINTER(_Window), C.POINTER(_Plane), i, vp], i),
+        "dctq_decode_bits_window_scaled_planes": ([vp, vp, vp, vp, C.POINTER(_Window), C.POINTER(_Plane), i, i, vp], i),
         "dctq_block_lengths": ([vp, ll, i, vp, vp, vp], i),
         "dctq_block_offsets_workspace_bytes": ([ll], C.c_size_t),
         "dctq_block_offsets": ([vp, i, ll, vp, vp, vp], i),
@@ -355,11 +356,13 @@ def _need_planes(outs, var_nums, recons, nbs, planes):
             _need(t, nb * per, dt, f"{name}[{k}]", px.device)
 
 
-def _decode_outs(what, n, shapes, outs, var_nums, devices, var_nbs=None):
+def _decode_outs(what, n, shapes, outs, var_nums, devices, var_nbs=None, unit=8):
     """The destination planes of decode_planes and the fused decoders: (outs, descs, nbs).
     shapes[k] is (F, H, W) or (H, W); outs[k], if given, a u8 tensor [F, H, W] or [H, W], possibly
     a strided view; one of the two is needed, and both must agree.  var_nums[k], if given, is
-    sized for var_nbs[k] blocks (None: plane k's own).  devices[k]: where outs[k] is allocated."""
+    sized for var_nbs[k] blocks (None: plane k's own).  devices[k]: where outs[k] is allocated.
+    unit: the pixels a block gives a destination's side (8; 4, 2 or 1 for a reduced picture,
+    where var_nbs is needed: nbs counts 8 x 8 blocks)."""
     import torch
     if shapes is None and outs is None:
         raise DctqError(f"{what} needs shapes or outs")
@@ -374,11 +377,50 @@ def _decode_outs(what, n, shapes, outs, var_nums, devices, var_nbs=None):
     for k, (d, o) in enumerate(zip(descs, outs)):
         if shapes is not None and (d.nframes, d.height, d.width) != shapes[k]:
             raise DctqError(f"outs[{k}] is {tuple(o.shape)}, shapes[{k}] says {shapes[k]}")
-        if d.width % 8 or d.height % 8:
-            raise DctqError(f"outs[{k}]: width and height must be multiples of 8")
+        if d.width % unit or d.height % unit:
+            raise DctqError(f"outs[{k}]: width and height must be multiples of {unit}")
         if var_nums is not None:
             _need(var_nums[k], (var_nbs or nbs)[k], torch.int32, f"var_nums[{k}]", o.device)
     return outs, descs, nbs
+
+
+def _stored_windows(shapes, windows):
+    """The windows of the window decoders, checked: shapes[k] the STORED (F, H, W) or (H, W) of
+    plane k, windows[k] = ((f0, f1), (y0, y1), (x0, x1)), half-open, y and x in pixels and
+    multiples of 8 -> (wins, wshapes, nbs): the _Window array a `const dctq_window *` parameter
+    takes, each window's own (F, H, W), and the stored planes' block counts."""
+    n = len(shapes)
+    if len(windows) != n:
+        raise DctqError(f"windows needs one entry per plane ({n}), got {len(windows)}")
+    shapes = _shapes3(shapes)
+    wins, wshapes = [], []
+    for k, ((f, h, w), win) in enumerate(zip(shapes, windows)):
+        try:
+            (f0, f1), (y0, y1), (x0, x1) = [tuple(map(int, r)) for r in win]
+        except (TypeError, ValueError):
+            raise DctqError(f"windows[{k}] must be ((f0, f1), (y0, y1), (x0, x1))") from None
+        if not _whole_blocks(f, h, w):
+            raise DctqError(f"shapes[{k}] {(f, h, w)}: height and width must be multiples of 8, nframes >= 1")
+        if not (0 <= f0 < f1 <= f and 0 <= y0 < y1 <= h and 0 <= x0 < x1 <= w):
+            raise DctqError(f"windows[{k}] {win} is empty or leaves the stored plane {(f, h, w)}")
+        if y0 % 8 or y1 % 8 or x0 % 8 or x1 % 8:
+            raise DctqError(f"windows[{k}] {win}: rows and columns must be multiples of 8")
+        wins.append(_Window(w, h, f, x0, y0, f0))
+        wshapes.append((f1 - f0, y1 - y0, x1 - x0))
+    nbs = [_nblocks(s) for s in shapes]
+    if sum(nbs) >= 1 << 26:
+        raise DctqError("more than 2^26 - 1 blocks in one decode")
+    return (_Window * n)(*wins), wshapes, nbs
+
+
+SCALES = {2: 1, 4: 2, 8: 3}   # scale -> log2_scale of dctq_decode_bits_window_scaled_planes
+
+
+def _log2_scale(scale) -> int:
+    """log2 of a reduction's scale, or DctqError: 2, 4 and 8 are all there is."""
+    if isinstance(scale, bool) or scale not in SCALES:
+        raise DctqError(f"scale must be 2, 4 or 8, got {scale!r}")
+    return SCALES[scale]
 
 
 class Plan:
@@ -642,15 +684,16 @@ class Plan:
                                              _stream_ptr(stream)))
         return outs
 
-    def _decode_stream(self, what, need, src, offsets, shapes, outs, var_nums, stream, launch, stored=None):
+    def _decode_stream(self, what, need, src, offsets, shapes, outs, var_nums, stream, launch, stored=None, unit=8):
         """The body of the fused decoders decode_symbols, decode_bits and decode_bits_window (what):
         the source checked by its validator (need: _need_symbols or _need_bytes), the destinations
         made or checked (_decode_outs), the offsets checked, all on one device, then the wrapper's
         own C call, launch(var_nums, descs, n, stream).  stored: the block counts the stream is
-        numbered over and var_nums are sized by, where they are not the destinations' own (a window)."""
+        numbered over and var_nums are sized by, where they are not the destinations' own (a window);
+        unit: as _decode_outs."""
         need(src)
         n = len(shapes if shapes is not None else outs if outs is not None else ())
-        outs, descs, nbs = _decode_outs(what, n, shapes, outs, var_nums, [src.device] * n, stored)
+        outs, descs, nbs = _decode_outs(what, n, shapes, outs, var_nums, [src.device] * n, stored, unit)
         _need_byte_offsets(offsets, sum(stored or nbs), src)
         if any(o.device != src.device for o in outs):
             raise DctqError(f"{'symbols' if need is _need_symbols else 'bytes'}, offsets and outs must be on one device")
@@ -693,35 +736,39 @@ class Plan:
         (bytes outside them are not touched); var_nums[k] (adaptive plans) is the whole stored
         plane's.  The work unit is a run of up to 64 blocks of one window row
         (tools/window_ref.py): a window narrower than 512 pixels leaves part of each wave idle."""
-        n = len(shapes)
-        if len(windows) != n:
-            raise DctqError(f"windows needs one entry per plane ({n}), got {len(windows)}")
-        shapes = _shapes3(shapes)
-        wins, wshapes = [], []
-        for k, ((f, h, w), win) in enumerate(zip(shapes, windows)):
-            try:
-                (f0, f1), (y0, y1), (x0, x1) = [tuple(map(int, r)) for r in win]
-            except (TypeError, ValueError):
-                raise DctqError(f"windows[{k}] must be ((f0, f1), (y0, y1), (x0, x1))") from None
-            if not _whole_blocks(f, h, w):
-                raise DctqError(f"shapes[{k}] {(f, h, w)}: height and width must be multiples of 8, nframes >= 1")
-            if not (0 <= f0 < f1 <= f and 0 <= y0 < y1 <= h and 0 <= x0 < x1 <= w):
-                raise DctqError(f"windows[{k}] {win} is empty or leaves the stored plane {(f, h, w)}")
-            if y0 % 8 or y1 % 8 or x0 % 8 or x1 % 8:
-                raise DctqError(f"windows[{k}] {win}: rows and columns must be multiples of 8")
-            wins.append(_Window(w, h, f, x0, y0, f0))
-            wshapes.append((f1 - f0, y1 - y0, x1 - x0))
-        nbs = [_nblocks(s) for s in shapes]
-        if sum(nbs) >= 1 << 26:
-            raise DctqError("more than 2^26 - 1 blocks in one decode")
+        wins, wshapes, nbs = _stored_windows(shapes, windows)
         if self.adaptive and var_nums is None:
             raise DctqError("adaptive decode needs var_nums")
-        wins = (_Window * n)(*wins)
         return self._decode_stream(
             "decode_bits_window", _need_bytes, bytes, offsets, wshapes, outs, var_nums, stream,
             lambda vn, descs, n, s: self._L.dctq_decode_bits_window_planes(
                 self._h, _ptr(bytes), _ptr(offsets), vn, wins, descs, n, s),
             stored=nbs)
+
+    def decode_bits_scaled(self, bytes, offsets, shapes, scale, windows=None, outs=None, var_nums=None, stream=None):
+        """A "bits v1" stream -> u8 pixels at 1 / scale size (scale 2, 4 or 8) in ONE launch, with
+        no full-size picture in between (dctq_decode_bits_window_scaled_planes): every stored
+        8 x 8 block gives n x n pixels, n = 8 / scale, from its n x n lowest coefficients, exactly
+        as include/dct_amd.h defines them (tools/scaled_ref.py applied to bits_decode(bytes,
+        offsets), byte for byte; for scale 8 the block's mean).  shapes, windows and var_nums as
+        decode_bits_window; windows None: the whole planes.  Returns the list of u8 tensors
+        [f1 - f0, (y1 - y0) / scale, (x1 - x0) / scale].  outs, if given, are those tensors and may
+        be strided views whose address and strides are multiples of n bytes (bytes outside them
+        are not touched).  The bit walk of a block stops after its corner, which is where the
+        time goes at full size."""
+        log2s = _log2_scale(scale)
+        shapes = _shapes3(shapes)
+        if windows is None:
+            windows = [((0, f), (0, h), (0, w)) for f, h, w in shapes]
+        wins, wshapes, nbs = _stored_windows(shapes, windows)
+        if self.adaptive and var_nums is None:
+            raise DctqError("adaptive decode needs var_nums")
+        return self._decode_stream(
+            "decode_bits_scaled", _need_bytes, bytes, offsets, [(f, h // scale, w // scale) for f, h, w in wshapes],
+            outs, var_nums, stream,
+            lambda vn, descs, n, s: self._L.dctq_decode_bits_window_scaled_planes(
+                self._h, _ptr(bytes), _ptr(offsets), vn, wins, descs, n, log2s, s),
+            stored=nbs, unit=8 >> log2s)
 
     def encode_bits_planes(self, planes, outs=None, capacity=None, stream=None, symbol_bytes=None):
         """encode_planes + bits_pack: forward, zigzag/RLE and the bit-packed stream of up to 4
@@ -1377,7 +1424,32 @@ def _region_windows(shapes, crops, colour, region, frames):
     return windows, cuts
 
 
-def decompress(buf, channels: int = 3, planar: bool = False, bgr: bool = False, stream=None, region=None, frames=None):
+def _decompress_scaled(d, plan, scale, frames, channels, planar, bgr, stream):
+    """decompress(scale=): the parts d of a container at 1 / scale size."""
+    import torch
+    windows, cuts = _region_windows(d["shapes"], d["crops"], d["colour"], None, frames)
+    small = [(-(-h // scale), -(-w // scale)) for _, _, h, w in cuts]   # of the TRUE sizes
+    kw = dict(var_nums=d["var_nums"], stream=stream)
+    if not d["colour"]:
+        outs = plan.decode_bits_scaled(d["bytes"], d["offsets"], d["shapes"], scale, windows, **kw)
+        return [o[:, :h, :w] for o, (h, w) in zip(outs, small)]
+    # Y, Cb, Cr into the top-left of planes of whole blocks, which is what ycbcr_to_rgb(size=) takes:
+    # the reduced chroma is exactly half the reduced luma, and a pixel inside `small` reads only
+    # bytes that were decoded (ceil(H / scale) <= stored H / scale)
+    sub = 2 if d["shapes"][1][1:] != d["shapes"][0][1:] else 1
+    m = 8 * sub
+    bh, bw = -(-small[0][0] // m) * m, -(-small[0][1] // m) * m
+    (f0, f1) = windows[0][0]
+    with _on_stream(stream):
+        bufs = [torch.empty((f1 - f0, bh // c, bw // c), dtype=torch.uint8, device=d["bytes"].device)
+                for c in (1, sub, sub)]
+    outs = [b[:, :(y1 - y0) // scale, :(x1 - x0) // scale] for b, (_, (y0, y1), (x0, x1)) in zip(bufs, windows)]
+    plan.decode_bits_scaled(d["bytes"], d["offsets"], d["shapes"], scale, windows, outs=outs, **kw)
+    return ycbcr_to_rgb(*bufs, channels=channels, planar=planar, bgr=bgr, stream=stream, size=small[0])
+
+
+def decompress(buf, channels: int = 3, planar: bool = False, bgr: bool = False, stream=None, region=None, frames=None,
+               scale=None):
     """The inverse of compress: frame_unpack, the container's plan, Plan.decode_bits and, for a
     colour container, ycbcr_to_rgb (channels / planar / bgr as there).  Returns the RGB stack
     [F, H, W, channels] for a colour container, the list of u8 planes [F, H, W] otherwise.
@@ -1394,10 +1466,23 @@ def decompress(buf, channels: int = 3, planar: bool = False, bgr: bool = False, 
     planes take one region when all planes have one true size, else a list of one region per
     plane; frames must lie inside every plane's.  A region or frame range that is empty or
     leaves the true picture raises DctqError before anything is decoded.  With neither given
-    the path and the result are those described first."""
+    the path and the result are those described first.
+    scale=2, 4 or 8 (optionally with frames): the pictures at 1 / scale size, decoded at that
+    size from the stream (Plan.decode_bits_scaled; include/dct_amd.h defines the pixels), for
+    frame v1 and frame c1 alike: plain planes as [F, ceil(H / scale), ceil(W / scale)] views, H
+    and W the TRUE size; a colour container as the RGB stack of that size, converted from the
+    reduced Y, Cb and Cr as every picture is.  scale together with region raises DctqError
+    (Plan.decode_bits_scaled takes windows), and so does any other scale."""
+    if scale is not None:
+        _log2_scale(scale)
+        if region is not None:
+            raise DctqError("decompress: scale together with region is not supported "
+                            "(Plan.decode_bits_scaled takes windows)")
     d = frame_unpack(buf, stream=stream)
     plan = _frame_plan(d["quality"], d["adaptive"], d["bytes"].device)
     crops = d["crops"]
+    if scale is not None:
+        return _decompress_scaled(d, plan, scale, frames, channels, planar, bgr, stream)
     if region is not None or frames is not None:
         windows, cuts = _region_windows(d["shapes"], crops, d["colour"], region, frames)
         outs = plan.decode_bits_window(d["bytes"], d["offsets"], d["shapes"], windows, var_nums=d["var_nums"],

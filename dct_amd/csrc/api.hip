@@ -322,10 +322,42 @@ int dctq_decode_bits_planes(const dctq_plan *plan, const uint8_t *bytes, const u
     return DCTQ_OK;
 }
 
-// The window decoder's planes: dst[k] placed in the stored plane win[k] describes, the stored
-// planes' concatenated block numbering and the run numbering (tools/window_ref.py).  Needs no
-// plan and no device, so every refusal of the geometry comes before either is looked at.
-static int window_set(const dctq_window *win, const dctq_plane *dst, int nplanes, dctq::WindowSet *out) {
+// plane_args for the reduced picture of the scaled window decoder: n = 8 / scale pixels a block
+// side, so everything plane_args asks in units of 8 is asked in units of n, and the block
+// counts are the window's.
+static int scaled_plane_args(const dctq_plane *s, int n, dctq::PlaneArgs *a) {
+    if (!s || !s->pixels) return fail(DCTQ_EINVAL, "plane/pixels is NULL");
+    if (s->width <= 0 || s->height <= 0 || s->width % n || s->height % n)
+        return fail(DCTQ_EINVAL, "scaled: dst width and height must be positive multiples of 8 / scale");
+    if (s->stride < s->width || s->stride % n)
+        return fail(DCTQ_EINVAL, "scaled: dst stride must be >= width and a multiple of 8 / scale");
+    if (misaligned(s->pixels, (uintptr_t)n) || s->frame_stride % n)
+        return fail(DCTQ_EINVAL, "scaled: dst pixels/frame_stride must be aligned to 8 / scale bytes");
+    if (s->nframes < 1) return fail(DCTQ_EINVAL, "nframes must be >= 1");
+    if (s->nframes > 1 && s->frame_stride < s->stride * (long long)s->height)
+        return fail(DCTQ_EINVAL, "frame_stride smaller than one frame");
+    const long long bw = s->width / n, bh = s->height / n, per = bw * bh, tot = per * s->nframes;
+    if (tot >= (1ll << 31) - 256) return fail(DCTQ_EINVAL, "more than 2^31 blocks in one call");
+    a->src = s->pixels;
+    a->stride = s->stride;
+    a->frame_stride = s->frame_stride;
+    a->bw = (int)bw;
+    a->nblk_frame = (int)per;
+    a->nblk = (int)tot;
+    a->div_bw = dctq::make_fastdiv((uint32_t)bw);
+    a->div_frame = dctq::make_fastdiv((uint32_t)per);
+    const long long span = (s->nframes - 1) * s->frame_stride + (s->height - 1) * s->stride + s->width;
+    a->span = span < 0xFFFFFFFFll ? (uint32_t)span : 0u;
+    return DCTQ_OK;
+}
+
+// The window decoders' planes: dst[k] placed in the stored plane win[k] describes, the stored
+// planes' concatenated block numbering and the run numbering (tools/window_ref.py).  log2_scale
+// 0: dst[k] is the window's own picture; 1..3: its reduction by 2, 4 or 8, so the window's
+// extent is dst[k]'s width and height times that.  Needs no plan and no device, so every
+// refusal of the geometry comes before either is looked at.
+static int window_set(const dctq_window *win, const dctq_plane *dst, int nplanes, int log2_scale,
+                      dctq::WindowSet *out) {
     if (!win || !dst) return fail(DCTQ_EINVAL, "win/dst is NULL");
     if (int rc = check_nplanes(nplanes)) return rc;
     dctq::WindowSet &ws = *out;
@@ -341,8 +373,10 @@ static int window_set(const dctq_window *win, const dctq_plane *dst, int nplanes
             return fail(DCTQ_EINVAL, "window: x0 and y0 must be non-negative multiples of 8");
         if (w.frame0 < 0) return fail(DCTQ_EINVAL, "window: frame0 must be >= 0");
         dctq::PlaneArgs &p = ws.pl[k];
-        if (int rc = dctq::plane_args(&dst[k], &p)) return rc;
-        if ((long long)w.x0 + dst[k].width > w.width || (long long)w.y0 + dst[k].height > w.height)
+        if (int rc = log2_scale ? scaled_plane_args(&dst[k], 8 >> log2_scale, &p) : dctq::plane_args(&dst[k], &p))
+            return rc;
+        const long long ww = (long long)dst[k].width << log2_scale, wh = (long long)dst[k].height << log2_scale;
+        if (w.x0 + ww > w.width || w.y0 + wh > w.height)
             return fail(DCTQ_EINVAL, "window: the region leaves the stored plane");
         if ((long long)w.frame0 + dst[k].nframes > w.nframes)
             return fail(DCTQ_EINVAL, "window: the frame range leaves the stored frames");
@@ -365,23 +399,45 @@ static int window_set(const dctq_window *win, const dctq_plane *dst, int nplanes
     return DCTQ_OK;
 }
 
-int dctq_decode_bits_window_planes(const dctq_plan *plan, const uint8_t *bytes, const uint32_t *offsets,
-                                   const int32_t *const *var_num, const dctq_window *win, const dctq_plane *dst,
-                                   int nplanes, void *stream) {
-    DCTQ_LAUNCH(stream, dctq::kEntryDecodeBitsWindowPlanes);
-    dctq::WindowSet ws;
-    if (int rc = window_set(win, dst, nplanes, &ws)) return rc;
+// What the window decoders check after the geometry: the plan (and its device), the stream's
+// pointers, and var_num where the plan is adaptive (into ws->var).
+static int window_source(const dctq_plan *plan, const uint8_t *bytes, const uint32_t *offsets,
+                         const int32_t *const *var_num, int nplanes, dctq::WindowSet *ws) {
     if (int rc = dctq::check_plan(plan)) return rc;
     if (!bytes || !offsets) return fail(DCTQ_EINVAL, "bytes/offsets is NULL");
     if (misaligned(offsets, 4)) return fail(DCTQ_EINVAL, "offsets must be 4-byte aligned");
     if (plan->adaptive && !var_num) return fail(DCTQ_EINVAL, "adaptive decode needs var_num");
     for (int k = 0; k < nplanes; ++k) {
         if (plan->adaptive && !var_num[k]) return fail(DCTQ_EINVAL, "adaptive decode needs every var_num[k]");
-        ws.var[k] = plan->adaptive ? var_num[k] : nullptr;
+        ws->var[k] = plan->adaptive ? var_num[k] : nullptr;
     }
+    return DCTQ_OK;
+}
+
+int dctq_decode_bits_window_planes(const dctq_plan *plan, const uint8_t *bytes, const uint32_t *offsets,
+                                   const int32_t *const *var_num, const dctq_window *win, const dctq_plane *dst,
+                                   int nplanes, void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryDecodeBitsWindowPlanes);
+    dctq::WindowSet ws;
+    if (int rc = window_set(win, dst, nplanes, 0, &ws)) return rc;
+    if (int rc = window_source(plan, bytes, offsets, var_num, nplanes, &ws)) return rc;
     HIPCHK(dctq::launch_decode_bits_window(ws, bytes, offsets, plan->dev, plan->adaptive, plan->inv_f32 != 0,
                                            (hipStream_t)stream, plan->num_cus),
            "decode_bits_window launch");
+    return DCTQ_OK;
+}
+
+int dctq_decode_bits_window_scaled_planes(const dctq_plan *plan, const uint8_t *bytes, const uint32_t *offsets,
+                                          const int32_t *const *var_num, const dctq_window *win,
+                                          const dctq_plane *dst, int nplanes, int log2_scale, void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryDecodeBitsWindowScaledPlanes);
+    if (log2_scale < 1 || log2_scale > 3) return fail(DCTQ_EINVAL, "scaled: log2_scale must be 1, 2 or 3");
+    dctq::WindowSet ws;
+    if (int rc = window_set(win, dst, nplanes, log2_scale, &ws)) return rc;
+    if (int rc = window_source(plan, bytes, offsets, var_num, nplanes, &ws)) return rc;
+    HIPCHK(dctq::launch_decode_bits_window_scaled(ws, bytes, offsets, plan->dev, plan->adaptive, log2_scale,
+                                                  (hipStream_t)stream, plan->num_cus),
+           "decode_bits_window_scaled launch");
     return DCTQ_OK;
 }
 

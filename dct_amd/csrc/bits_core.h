@@ -71,7 +71,11 @@ static_assert(kBitsStage % 256 == 0 && kBitsStage - 3 >= 2 * 33 * 64 / 8, "whole
 // bytes: the stream; offv: lane b holds offsets[64t + b] (lanes >= nb: the tile's end); oend:
 // the tile's end.  Blocks [h, he) of the tile -> rows at lt + i * kDecPitch (the pitch is
 // returned); the stage is the kBitsStage bytes behind the half tile.  A source of decode_tiles
-// (tile_decode_core.h), whose per-lane block lengths it does not need.
+// (tile_decode_core.h), whose per-lane block lengths it does not need.  END: the walk of a
+// block stops once its position has reached END; positions only increase, so every value at a
+// zigzag position below END is what the full walk (END = 64, every full-size decoder) places
+// there, and the rows hold nothing a caller may rely on at or beyond it (decode_scaled.hip).
+template <uint32_t END = 64u>
 __device__ __forceinline__ int bits_rebuild_half(const uint8_t *__restrict__ bytes, uint32_t offv, uint32_t oend,
                                                  uint32_t /* cnt_lane */, int h, int he, int lane, char *lt,
                                                  const uint8_t (*zz)[64]) {
@@ -142,7 +146,7 @@ __device__ __forceinline__ int bits_rebuild_half(const uint8_t *__restrict__ byt
                 have -= bits;
                 return true;
             };
-            for (uint32_t i = 0; i < kBitsMaxSymbols && pos < 64u; ++i) {
+            for (uint32_t i = 0; i < kBitsMaxSymbols && pos < END; ++i) {
                 uint32_t r, m;
                 if (!get(r) || !get(m)) break;
                 pos += r;

@@ -68,8 +68,9 @@ enum Entry : int {
     kEntryYcbcrToRgbCropPlanes,
     kEntryPadPlanes,
     kEntryDecodeBitsWindowPlanes,
+    kEntryDecodeBitsWindowScaledPlanes,
 };
-static_assert(kEntryDecodeBitsWindowPlanes < 32, "LaunchIsolation keeps one bit per entry point in a uint32_t");
+static_assert(kEntryDecodeBitsWindowScaledPlanes < 32, "LaunchIsolation keeps one bit per entry point in a uint32_t");
 class LaunchIsolation {
   public:
     LaunchIsolation(const void *stream, Entry entry);
@@ -265,7 +266,10 @@ struct SymbolSet {
 // The window decoder's planes (decode_window.hip): pl[k].src is the DESTINATION, the window's
 // own picture, so pl[k].bw is the window's width in blocks; win[k] places it in the stored
 // plane.  A run is up to 64 consecutive stored blocks of one window row (tools/window_ref.py);
-// runs are numbered over window rows, frames, planes.
+// runs are numbered over window rows, frames, planes.  The scaled decoder (decode_scaled.hip)
+// takes the same set: there pl[k] describes the REDUCED picture, n = 8 / scale pixels a block
+// side, so stride, frame_stride and span are the reduced picture's and bw, nblk_frame and nblk
+// still count the window's blocks.
 struct WindowPlane {
     uint32_t first;       // the window's first block in the concatenated stored numbering (offsets' index)
     uint32_t var_first;   // ... and inside its stored plane (var_num's index)
@@ -428,6 +432,10 @@ hipError_t launch_decode_bits(const SymbolSet &ss, const uint8_t *bytes, const u
 hipError_t launch_decode_bits_window(const WindowSet &ws, const uint8_t *bytes, const uint32_t *offsets,
                                      const DevTables *dev, int adaptive, bool inv_f32, hipStream_t stream,
                                      int num_cus);
+// ... at 1/2, 1/4 or 1/8 size (log2_scale 1, 2, 3): n x n pixels a block, n = 8 >> log2_scale (decode_scaled.hip)
+hipError_t launch_decode_bits_window_scaled(const WindowSet &ws, const uint8_t *bytes, const uint32_t *offsets,
+                                            const DevTables *dev, int adaptive, int log2_scale, hipStream_t stream,
+                                            int num_cus);
 // byte offsets of a packed stream <-> one or two bytes of length per block (frame.hip); ws: rle_workspace_bytes(nblk)
 hipError_t launch_block_lengths(const uint32_t *offsets, long long nblk, int length_bytes, void *lengths,
                                 uint32_t *max_length, hipStream_t stream, int num_cus);

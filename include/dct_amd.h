@@ -353,6 +353,50 @@ int dctq_decode_bits_window_planes(const dctq_plan *plan, const uint8_t *bytes, 
                                    const int32_t *const *var_num, const dctq_window *win,
                                    const dctq_plane *dst, int nplanes, void *stream);
 
+/* The same window at 1/2, 1/4 or 1/8 size, straight from the packed stream in ONE
+ * launch (what libjpeg's scale_denom gives a JPEG viewer): log2_scale 1, 2 or 3,
+ * scale s = 2, 4, 8 and n = 8 / s, so every stored 8 x 8 block gives n x n pixels.
+ * bytes, offsets, var_num and win[k] are as for dctq_decode_bits_window_planes (a
+ * whole stored plane is simply the full window).  dst[k] is the REDUCED picture:
+ * its width * s x height * s x nframes is the window's extent; width and height
+ * are positive multiples of n (they need not be multiples of 8), pixels, stride
+ * and frame_stride multiples of n bytes, stride >= width.  Bytes of dst outside
+ * width x height of each frame are not touched.
+ *   Definition (tools/scaled_ref.py states it in plain numpy).  Everything is IEEE
+ *   fp64; every multiply and add is rounded separately (no fma); sums run left to
+ *   right in ascending index.  Only the coefficients q[u][v], u, v < n, of a block
+ *   are used (Q: the plan's quantization table, var_num: the block's):
+ *     non-adaptive plans   x[u][v] = (double)q[u][v] * (1.0 / Q[u][v])
+ *                          (the multiplication by 1 / Q of every decoder here)
+ *     adaptive plans       sc = 2.0 - fmin(1.0, fmax(0.1, (var_num / 4096.0) / 1000.0))
+ *                          x[u][v] = ((double)q[u][v] * Q[u][v]) * sc
+ *                          x[0][0] = (double)q[0][0] * Q[0][0]
+ *     temp[u][j] = sum over v of x[u][v] * Dn[v][j]
+ *     out[i][j]  = sum over u of Dn[u][i] * temp[u][j]
+ *     R          = out[i][j] * (n / 8.0) + 128.0
+ *     pixel      = (uint8_t)rint(fmin(fmax(R, 0.0), 255.0)), ties to even
+ *   with Dn the n-point DCT matrix as these literals (never through cos):
+ *     D1 = [[1.0]]
+ *     D2 = [[r, r], [r, -r]],  r = 0x1.6a09e667f3bcdp-1
+ *     D4 = [[h, h, h, h], [a, b, -b, -a], [h, -h, -h, h], [b, -a, a, -b]],
+ *          h = 0.5, a = 0x1.4e7ae9144f0fcp-1, b = 0x1.1517a7bdb3896p-2
+ *   For s = 8 a pixel is the dequantized DC / 8 + 128: the block's mean.
+ *   The pixels are exactly these for any bytes and any non-decreasing offsets: the
+ *   coefficients are those dctq_bits_decode gives.  In zigzag order the n x n corner
+ *   ends at position 24, 4 or 0, and the bit walk of a block stops once it is past
+ *   it (positions only increase).
+ * The read contract is the window decoder's: a run of nb blocks from stored block
+ * s0 reads offsets[s0 .. s0 + nb] and nothing outside [offsets[s0], offsets[s0 + nb])
+ * of the bytes.  DCTQ_EINVAL, before any launch and before a device is looked at:
+ * log2_scale outside 1..3; a dst that breaks the rules above (or NULL pixels,
+ * nframes < 1, a frame_stride below one frame); every geometry
+ * dctq_decode_bits_window_planes refuses.  Then, as there: a NULL plan, bytes or
+ * offsets; missing var_num on an adaptive plan.  Asynchronous on stream; allocates
+ * nothing. */
+int dctq_decode_bits_window_scaled_planes(const dctq_plan *plan, const uint8_t *bytes, const uint32_t *offsets,
+                                          const int32_t *const *var_num, const dctq_window *win,
+                                          const dctq_plane *dst, int nplanes, int log2_scale, void *stream);
+
 /* Self-contained container, format "frame v1": everything a decoder of a "bits
  * v1" stream needs, in one byte buffer (tools/frame_ref.py states it in plain
  * Python).  Little-endian.  A block of bits v1 is at most 368 B, so the N + 1
