@@ -36,6 +36,10 @@ class _Window(C.Structure):
                 ("x0", C.c_int), ("y0", C.c_int), ("frame0", C.c_int)]
 
 
+class _Extent(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("nframes", C.c_int)]
+
+
 class _Rgb(C.Structure):
     _fields_ = [("pixels", C.c_void_p), ("stride", C.c_longlong), ("frame_stride", C.c_longlong),
                 ("channel_stride", C.c_longlong), ("pixel_step", C.c_int),
@@ -111,6 +115,9 @@ def _bind(L: C.CDLL, diagnostic: bool) -> C.CDLL:
         "dctq_decode_bits_planes": ([vp, vp, vp, vp, C.POINTER(_Plane), i, vp], i),
         "dctq_decode_bits_window_planes": ([vp, vp, vp, vp, C.POINTER(_Window), C.POINTER(_Plane), i, vp], i),
         "dctq_decode_bits_window_scaled_planes": ([vp, vp, vp, vp, C.POINTER(_Window), C.POINTER(_Plane), i, i, vp], i),
+        "dctq_bits_window_workspace_bytes": ([ll], C.c_size_t),
+        "dctq_bits_window_offsets": ([vp, vp, C.POINTER(_Window), C.POINTER(_Extent), i, vp, vp, vp, vp], i),
+        "dctq_bits_window_gather": ([vp, vp, C.POINTER(_Window), C.POINTER(_Extent), i, vp, vp, C.c_size_t, vp], i),
         "dctq_block_lengths": ([vp, ll, i, vp, vp, vp], i),
         "dctq_block_offsets_workspace_bytes": ([ll], C.c_size_t),
         "dctq_block_offsets": ([vp, i, ll, vp, vp, vp], i),
@@ -925,6 +932,42 @@ def bits_decode(bytes, offsets, out=None, stream=None):
     return out
 
 
+def bits_window(bytes, offsets, shapes, windows, var_nums=None, stream=None):
+    """A window of every plane of a "bits v1" stream as a stream of its own, without decoding
+    (dctq_bits_window_offsets, dctq_bits_window_gather; tools/extract_ref.py window_stream gives
+    the same bytes): the stored stream's blocks inside the windows, numbered as the window's own
+    picture numbers them, so Plan.decode_bits(bytes', offsets', window shapes) is bit for bit
+    Plan.decode_bits_window(bytes, offsets, shapes, windows).  bytes, offsets, shapes, windows and
+    var_nums are as Plan.decode_bits_window takes them (var_nums[k] the whole stored plane's; any
+    bytes, any non-decreasing offsets).  Returns (bytes' uint8 [total], offsets' int32 [N' + 1]
+    holding uint32 bit patterns, var_nums': per-plane int32 views of one array, or None).  Reads
+    the window's payload size back (one sync) and allocates exactly that."""
+    import torch
+    wins, wshapes, nbs = _stored_windows(shapes, windows)
+    _need_bytes(bytes)
+    _need_byte_offsets(offsets, sum(nbs), bytes)
+    n, dev = len(wshapes), bytes.device
+    if var_nums is not None:
+        if len(var_nums) != n:
+            raise DctqError(f"var_nums needs one entry per plane ({n}), got {len(var_nums)}")
+        for k, v in enumerate(var_nums):
+            _need(v, nbs[k], torch.int32, f"var_nums[{k}]", dev)
+    exts = (_Extent * n)(*[_Extent(w, h, f) for f, h, w in wshapes])
+    wnbs = [_nblocks(s) for s in wshapes]
+    total_blocks = sum(wnbs)
+    L, s = lib(), _stream_ptr(stream)
+    ws = _workspace(L.dctq_bits_window_workspace_bytes, total_blocks, dev)
+    woff = torch.empty(total_blocks + 1, dtype=torch.int32, device=dev)
+    wvar = torch.empty(total_blocks, dtype=torch.int32, device=dev) if var_nums is not None else None
+    _check(L.dctq_bits_window_offsets(_ptr(offsets), _ptrs(var_nums), wins, exts, n, _ptr(woff), _ptr(wvar),
+                                      _ptr(ws), s), L)
+    total = _read_back(woff[total_blocks:], stream)[0]
+    out = torch.empty(total, dtype=torch.uint8, device=dev)
+    if total:
+        _check(L.dctq_bits_window_gather(_ptr(bytes), _ptr(offsets), wins, exts, n, _ptr(woff), _ptr(out), total, s), L)
+    return out, woff, (list(torch.split(wvar, wnbs)) if wvar is not None else None)
+
+
 def rgb_desc(t, bgr: bool = False):
     """Describe a uint8 device tensor [F, H, W, C] or [H, W, C] (channel axis last in the shape,
     C 3 or 4) as an RGB picture stack, without a copy.  Unit channel stride and a pixel stride of
@@ -1212,7 +1255,8 @@ def _frame_header(head: bytes, buflen: int) -> dict:
             "shapes": shapes, "nblocks": nblocks, "payload_bytes": payload_bytes, "starts": starts, "crops": crops}
 
 
-def frame_pack(bytes, offsets, shapes, quality, adaptive=False, var_nums=None, colour=False, stream=None, crops=None):
+def frame_pack(bytes, offsets, shapes, quality, adaptive=False, var_nums=None, colour=False, stream=None, crops=None,
+               length_bytes=None):
     """A packed stream and what its decoder must know -> one uint8 device tensor, the container
     "frame v1" (include/dct_amd.h; tools/frame_ref.py pack gives the same bytes).  bytes / offsets
     as bits_pack or Plan.encode_bits_planes return them; shapes[k] is (F, H, W) or (H, W) of plane
@@ -1222,7 +1266,8 @@ def frame_pack(bytes, offsets, shapes, quality, adaptive=False, var_nums=None, c
     into one allocation.  Reads the largest length and the total back (two syncs).  crops: per
     plane (pad_bottom, pad_right), the rows and columns of the stored plane to drop after decoding;
     with any of them non-zero the container is "frame c1" (magic DCTQFRC1), with None or all zero
-    it is frame v1, byte for byte."""
+    it is frame v1, byte for byte.  length_bytes None: 1 when every block is at most 255 B, else
+    2 (as block_lengths chooses); 1 or 2 asks for that width (frame_concat keeps its sources' 2)."""
     import struct
     import torch
     _need_bytes(bytes)
@@ -1237,7 +1282,7 @@ def frame_pack(bytes, offsets, shapes, quality, adaptive=False, var_nums=None, c
     _need_byte_offsets(offsets, nblocks, bytes)
     dev = bytes.device
     sections = []
-    lengths, lb = block_lengths(offsets, stream=stream)
+    lengths, lb = block_lengths(offsets, length_bytes, stream=stream)
     sections.append(lengths.view(torch.uint8))
     first, total = _read_back(offsets[[0, nblocks]], stream)
     if first != 0 or total != bytes.numel():
@@ -1275,6 +1320,12 @@ def frame_unpack(buf, stream=None) -> dict:
     payload, a view into buf: what Plan.decode_bits takes with offsets) and var_nums (adaptive:
     a list of int32 views into buf, one per plane; else None), and crops: None for frame v1, for
     frame c1 the list of (pad_bottom, pad_right) per plane."""
+    return _frame_parts(*_frame_open(buf, stream), stream)
+
+
+def _frame_open(buf, stream):
+    """frame_unpack's first half: buf on the device, and its header checked on the host
+    (_frame_header) -> (buf, h).  Nothing is launched but the copies."""
     import torch
     if isinstance(buf, torch.Tensor):
         if not buf.is_cuda or buf.dtype != torch.uint8 or buf.dim() != 1:
@@ -1292,7 +1343,12 @@ def frame_unpack(buf, stream=None) -> dict:
         raise DctqError("frame: shorter than the 48-byte fixed header")
     with _on_stream(stream):
         head = buf[:_FRAME_HEAD].cpu().numpy().tobytes()
-    h = _frame_header(head, buf.numel())
+    return buf, _frame_header(head, buf.numel())
+
+
+def _frame_parts(buf, h, stream):
+    """frame_unpack's second half: the offsets rebuilt on the device and the sections as views."""
+    import torch
     n, lb, starts = h["nblocks"], h["length_bytes"], h["starts"]
     lengths = buf[starts[0]:starts[0] + n * lb]
     offsets = block_offsets(lengths if lb == 1 else lengths.view(torch.int16), stream=stream)
@@ -1501,6 +1557,100 @@ def decompress(buf, channels: int = 3, planar: bool = False, bgr: bool = False, 
         return [o[:, :o.shape[1] - pb, :o.shape[2] - pr] for o, (pb, pr) in zip(outs, crops)]
     size = None if crops is None else (outs[0].shape[1] - crops[0][0], outs[0].shape[2] - crops[0][1])
     return ycbcr_to_rgb(*outs, channels=channels, planar=planar, bgr=bgr, stream=stream, size=size)
+
+
+def _window_crops(shapes, crops, colour, region, frames):
+    """frame_window's region arithmetic, on the host: decompress's (_region_windows), with the one
+    rule a stream adds -- a region starts on a multiple of m (8; 16 for a 4:2:0 picture), since a
+    stream cannot begin inside a block -> (windows, wshapes, crops'): the stored windows, their own
+    (F, H, W), and what the new container records, (window height - region height, window width -
+    region width) on plane 0 of a picture or per plane for plain planes, (0, 0) elsewhere."""
+    windows, cuts = _region_windows(shapes, crops, colour, region, frames)
+    m = 16 if colour and shapes[1][1:] != shapes[0][1:] else 8
+    if any(dy or dx for dy, dx, _, _ in cuts):
+        raise DctqError(f"frame_window: a region must start on multiples of {m} (a stream cannot begin inside a "
+                        f"block), got rows and columns from {[(w[1][0] + c[0], w[2][0] + c[1]) for w, c in zip(windows, cuts)]}")
+    wshapes = [(f1 - f0, y1 - y0, x1 - x0) for (f0, f1), (y0, y1), (x0, x1) in windows]
+    new = [(wh - h, ww - w) for (_, wh, ww), (_, _, h, w) in zip(wshapes, cuts)]
+    return windows, wshapes, new + [(0, 0)] * (len(shapes) - len(new))
+
+
+def frame_window(buf, region=None, frames=None, stream=None):
+    """A region and / or a frame range of a container (frame v1 or frame c1) as a container of its
+    own, without decoding: frame_unpack, decompress's region arithmetic, bits_window, frame_pack
+    (tools/extract_ref.py frame_window gives the same bytes).  Quality, adaptive and colour are
+    carried over; length_bytes is chosen from the window's own blocks.  region=((y0, y1), (x0,
+    x1)) in pixels of the TRUE picture (plain planes: one region, or a list of one per plane),
+    frames=(f0, f1), both half-open, as for decompress -- but a region must START on multiples of
+    m (8; 16 for a 4:2:0 picture), or DctqError is raised before anything is launched.  It may end
+    anywhere inside the true picture: the window is grown to multiples of m, and the new container
+    records the difference as its crop (frame c1; frame v1 when there is none).  Lossless:
+    decompress(frame_window(buf, region, frames), ...) is byte for byte decompress(buf,
+    region=region, frames=frames, ...), and where the region ends on multiples of m or on the true
+    picture's edge, frame_window(compress(x, ...), region, frames) is byte for byte
+    compress(x[f0:f1, y0:y1, x0:x1], ...)."""
+    buf, h = _frame_open(buf, stream)
+    windows, wshapes, crops = _window_crops(h["shapes"], h["crops"], h["colour"], region, frames)
+    d = _frame_parts(buf, h, stream)
+    packed, off, var = bits_window(d["bytes"], d["offsets"], d["shapes"], windows, d["var_nums"], stream=stream)
+    return frame_pack(packed, off, wshapes, d["quality"], d["adaptive"], var, d["colour"], stream=stream, crops=crops)
+
+
+def frame_concat(bufs, stream=None):
+    """Two or more containers joined along the frame axis, without decoding: the inverse of
+    frame_window(frames=) (tools/extract_ref.py frame_concat gives the same bytes).  The sources
+    must agree in quality, adaptive, colour, the number of planes, every plane's stored (H, W) and
+    crops, else DctqError; so do more than 11 671 106 blocks or a payload of 2^32 bytes or more.
+    Blocks are numbered plane by plane, so plane k of the result is plane k of each source in turn,
+    in the lengths, var_num and payload sections alike: device slices and copies, with the plane
+    boundaries' offsets read back (one sync a source).  length_bytes is 2 if any source's is 2.
+    frame_concat([frame_window(b, frames=(0, a)), frame_window(b, frames=(a, F))]) is b byte for
+    byte for any b that compress wrote, and frame_concat([compress(x[:a]), compress(x[a:])]) is
+    compress(x)."""
+    import torch
+    bufs = list(bufs)
+    if len(bufs) < 2:
+        raise DctqError("frame_concat needs two or more containers")
+    ds = [frame_unpack(b, stream=stream) for b in bufs]
+    a = ds[0]
+    for i, d in enumerate(ds[1:], 1):
+        for key in ("quality", "adaptive", "colour", "crops"):
+            if d[key] != a[key]:
+                raise DctqError(f"frame_concat: container {i} differs from container 0 in {key}: {d[key]} != {a[key]}")
+        if len(d["shapes"]) != len(a["shapes"]) or [s[1:] for s in d["shapes"]] != [s[1:] for s in a["shapes"]]:
+            raise DctqError(f"frame_concat: container {i} differs from container 0 in its planes' stored sizes")
+        if d["bytes"].device != a["bytes"].device:
+            raise DctqError("frame_concat: the containers must be on one device")
+    nplanes = len(a["shapes"])
+    shapes = [(sum(d["shapes"][k][0] for d in ds), *a["shapes"][k][1:]) for k in range(nplanes)]
+    nblocks = sum(_nblocks(s) for s in shapes)
+    if nblocks > _FRAME_MAX_BLOCKS:
+        raise DctqError(f"frame_concat: {nblocks} blocks, a container holds at most {_FRAME_MAX_BLOCKS}")
+    if sum(d["bytes"].numel() for d in ds) >= 1 << 32:
+        raise DctqError("frame_concat: the payload must stay below 2^32 bytes")
+    # each source's plane boundaries: block numbers, and their byte offsets read back
+    firsts, cuts = [], []
+    for d in ds:
+        first = [0]
+        for s in d["shapes"]:
+            first.append(first[-1] + _nblocks(s))
+        firsts.append(first)
+        cuts.append(_read_back(d["offsets"][first], stream))
+    offs, pays, base = [], [], 0
+    with _on_stream(stream):
+        for k in range(nplanes):
+            for d, first, cut in zip(ds, firsts, cuts):
+                shift = (base - cut[k]) & 0xFFFFFFFF    # uint32 arithmetic in int32 bit patterns
+                offs.append(d["offsets"][first[k]:first[k + 1]] + (shift - (1 << 32) if shift >> 31 else shift))
+                pays.append(d["bytes"][cut[k]:cut[k + 1]])
+                base += cut[k + 1] - cut[k]
+        offs.append(torch.tensor([base - (1 << 32) if base >> 31 else base], dtype=torch.int32, device=offs[0].device))
+        off, packed = torch.cat(offs), torch.cat(pays)
+        var = None
+        if a["adaptive"]:
+            var = torch.cat([d["var_nums"][k] for k in range(nplanes) for d in ds])
+    return frame_pack(packed, off, shapes, a["quality"], a["adaptive"], var, a["colour"], stream=stream, crops=a["crops"],
+                      length_bytes=max(d["length_bytes"] for d in ds))
 
 
 def symbol_bytes(quality: int, adaptive: bool = False) -> int:

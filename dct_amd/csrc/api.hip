@@ -441,6 +441,66 @@ int dctq_decode_bits_window_scaled_planes(const dctq_plan *plan, const uint8_t *
     return DCTQ_OK;
 }
 
+// The stream extraction's windows: window_set over planes that stand for the extents (a window's
+// own picture as a dense plane that is never touched), so the geometry is the window decoder's
+// check and not a copy of it.
+static int extent_window_set(const dctq_window *win, const dctq_extent *ext, int nplanes, dctq::WindowSet *ws) {
+    alignas(8) static const uint8_t no_pixels[8] = {};
+    if (!win || !ext) return fail(DCTQ_EINVAL, "win/ext is NULL");
+    if (int rc = check_nplanes(nplanes)) return rc;
+    dctq_plane dst[dctq::kMaxPlanes];
+    for (int k = 0; k < nplanes; ++k)
+        dst[k] = {no_pixels, ext[k].width, (long long)ext[k].width * ext[k].height, ext[k].width, ext[k].height,
+                  ext[k].nframes};
+    return window_set(win, dst, nplanes, 0, ws);
+}
+
+static int device_cus();
+
+size_t dctq_bits_window_workspace_bytes(long long window_blocks) { return scan_workspace_bytes(window_blocks); }
+
+int dctq_bits_window_offsets(const uint32_t *offsets, const int32_t *const *var_num, const dctq_window *win,
+                             const dctq_extent *ext, int nplanes, uint32_t *win_offsets, int32_t *win_var_num,
+                             void *workspace, void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryBitsWindowOffsets);
+    dctq::WindowSet ws;
+    if (int rc = extent_window_set(win, ext, nplanes, &ws)) return rc;
+    if (!offsets || !win_offsets) return fail(DCTQ_EINVAL, "offsets/win_offsets is NULL");
+    if (misaligned(offsets, 4) || misaligned(win_offsets, 4))
+        return fail(DCTQ_EINVAL, "offsets and win_offsets must be 4-byte aligned");
+    if (var_num) {
+        if (!win_var_num || misaligned(win_var_num, 4))
+            return fail(DCTQ_EINVAL, "var_num given but win_var_num is NULL or not 4-byte aligned");
+        for (int k = 0; k < nplanes; ++k) {
+            if (!var_num[k] || misaligned(var_num[k], 4))
+                return fail(DCTQ_EINVAL, "var_num given but var_num[k] is NULL or not 4-byte aligned");
+            ws.var[k] = var_num[k];
+        }
+    }
+    if (int rc = check_workspace(workspace)) return rc;
+    HIPCHK(dctq::launch_bits_window_offsets(ws, offsets, win_offsets, var_num ? win_var_num : nullptr, workspace,
+                                            (hipStream_t)stream, device_cus()),
+           "bits_window_offsets launch");
+    return DCTQ_OK;
+}
+
+int dctq_bits_window_gather(const uint8_t *bytes, const uint32_t *offsets, const dctq_window *win,
+                            const dctq_extent *ext, int nplanes, const uint32_t *win_offsets, uint8_t *win_bytes,
+                            size_t capacity, void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryBitsWindowGather);
+    dctq::WindowSet ws;
+    if (int rc = extent_window_set(win, ext, nplanes, &ws)) return rc;
+    if (!bytes || !offsets || !win_offsets || !win_bytes)
+        return fail(DCTQ_EINVAL, "bytes/offsets/win_offsets/win_bytes is NULL");
+    if (misaligned(offsets, 4) || misaligned(win_offsets, 4))
+        return fail(DCTQ_EINVAL, "offsets and win_offsets must be 4-byte aligned");
+    if (!capacity) return DCTQ_OK;
+    HIPCHK(dctq::launch_bits_window_gather(ws, bytes, offsets, win_offsets, win_bytes, (unsigned long long)capacity,
+                                           (hipStream_t)stream, device_cus()),
+           "bits_window_gather launch");
+    return DCTQ_OK;
+}
+
 int dctq_synth(uint64_t seed, int kind, const dctq_plane *dst, void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntrySynth);
     if (!dst || !dst->pixels) return fail(DCTQ_EINVAL, "dst is NULL");

@@ -69,8 +69,10 @@ enum Entry : int {
     kEntryPadPlanes,
     kEntryDecodeBitsWindowPlanes,
     kEntryDecodeBitsWindowScaledPlanes,
+    kEntryBitsWindowOffsets,
+    kEntryBitsWindowGather,
 };
-static_assert(kEntryDecodeBitsWindowScaledPlanes < 32, "LaunchIsolation keeps one bit per entry point in a uint32_t");
+static_assert(kEntryBitsWindowGather < 32, "LaunchIsolation keeps one bit per entry point in a uint32_t");
 class LaunchIsolation {
   public:
     LaunchIsolation(const void *stream, Entry entry);
@@ -436,6 +438,14 @@ hipError_t launch_decode_bits_window(const WindowSet &ws, const uint8_t *bytes, 
 hipError_t launch_decode_bits_window_scaled(const WindowSet &ws, const uint8_t *bytes, const uint32_t *offsets,
                                             const DevTables *dev, int adaptive, int log2_scale, hipStream_t stream,
                                             int num_cus);
+// a window of a packed stream as a stream of its own (extract.hip): its offsets (and gathered var_num, if
+// win_var is set; ws.var is then the stored planes'), then its bytes below `capacity`; wsp:
+// rle_workspace_bytes(the window's blocks)
+hipError_t launch_bits_window_offsets(const WindowSet &ws, const uint32_t *offsets, uint32_t *win_offsets,
+                                      int32_t *win_var, void *wsp, hipStream_t stream, int num_cus);
+hipError_t launch_bits_window_gather(const WindowSet &ws, const uint8_t *bytes, const uint32_t *offsets,
+                                     const uint32_t *win_offsets, uint8_t *win_bytes, unsigned long long capacity,
+                                     hipStream_t stream, int num_cus);
 // byte offsets of a packed stream <-> one or two bytes of length per block (frame.hip); ws: rle_workspace_bytes(nblk)
 hipError_t launch_block_lengths(const uint32_t *offsets, long long nblk, int length_bytes, void *lengths,
                                 uint32_t *max_length, hipStream_t stream, int num_cus);

@@ -397,6 +397,54 @@ int dctq_decode_bits_window_scaled_planes(const dctq_plan *plan, const uint8_t *
                                           const int32_t *const *var_num, const dctq_window *win,
                                           const dctq_plane *dst, int nplanes, int log2_scale, void *stream);
 
+/* A window of a packed stream as a packed stream of its own, without decoding: no
+ * block of bits v1 depends on another (no DC prediction, no tables, var_num per
+ * block), so the stream of a block-aligned sub-picture is the sub-sequence of the
+ * stored stream's blocks, and these two calls only move bytes.  win[k] is as for
+ * dctq_decode_bits_window_planes; ext[k] is the window's extent in stored plane k
+ * (where the decoder's dst[k] gave it), width and height positive multiples of 8.
+ * The destination numbers the window's N' blocks as the window's own picture does:
+ * plane by plane, then frames, block rows, block columns -- what
+ * dctq_decode_bits_planes expects for planes of the extents.  For destination
+ * block d that is stored block s (d_k, s_k inside plane k)
+ *   win_offsets[d + 1] - win_offsets[d] = offsets[s + 1] - offsets[s]  (mod 2^32,
+ *                                         exact: no clamp to 368),  win_offsets[0] = 0
+ *   win_bytes[win_offsets[d] .. win_offsets[d + 1]) = bytes[offsets[s] .. offsets[s + 1])
+ *   win_var_num[d] = var_num[k][s_k]
+ * for any bytes and any non-decreasing offsets (tools/extract_ref.py states it in
+ * plain numpy).  The window's payload cannot exceed the stream's, so 32-bit
+ * offsets cannot wrap.
+ * dctq_bits_window_offsets writes win_offsets[0 .. N'] (win_offsets[N'] is the
+ * window's payload size) and, when var_num is not NULL, win_var_num[0 .. N') (one
+ * array, the planes concatenated; var_num[k] is the whole stored plane's).  It
+ * reads offsets[s] and offsets[s + 1] of the window's blocks only.  workspace:
+ * device memory of dctq_bits_window_workspace_bytes(N') bytes, 4-byte aligned.
+ * dctq_bits_window_gather writes the bytes, given the win_offsets of the first
+ * call: one wave per run of the window decoder, a run being one contiguous byte
+ * copy.  Nothing outside [offsets[s0], offsets[s0 + nb]) of a run is read and
+ * nothing outside [win_offsets[d0], min(win_offsets[d0 + nb], capacity)) is
+ * written: no byte at or past win_bytes + capacity, so a short buffer gets the
+ * payload's first `capacity` bytes.  bytes and win_bytes may sit at any alignment
+ * (source and destination alignment of a run are independent anyway); offsets,
+ * win_offsets, var_num[k] and win_var_num are 4-byte aligned.  About 8 B read and
+ * 4 B written per block by the first call (+ 8 B adaptive), P read and P written by
+ * the second (P: the block's packed bytes).
+ * DCTQ_EINVAL, before any launch and before a device is looked at: NULL win or ext;
+ * an extent whose width or height is not a positive multiple of 8, or nframes < 1;
+ * every geometry dctq_decode_bits_window_planes refuses (through the same check);
+ * then a NULL or misaligned pointer, or var_num without win_var_num.  Asynchronous
+ * on stream; allocate nothing. */
+typedef struct dctq_extent {
+    int width, height, nframes;   /* a window's extent in its stored plane; width and height multiples of 8 */
+} dctq_extent;
+size_t dctq_bits_window_workspace_bytes(long long window_blocks);
+int dctq_bits_window_offsets(const uint32_t *offsets, const int32_t *const *var_num, const dctq_window *win,
+                             const dctq_extent *ext, int nplanes, uint32_t *win_offsets, int32_t *win_var_num,
+                             void *workspace, void *stream);
+int dctq_bits_window_gather(const uint8_t *bytes, const uint32_t *offsets, const dctq_window *win,
+                            const dctq_extent *ext, int nplanes, const uint32_t *win_offsets, uint8_t *win_bytes,
+                            size_t capacity, void *stream);
+
 /* Self-contained container, format "frame v1": everything a decoder of a "bits
  * v1" stream needs, in one byte buffer (tools/frame_ref.py states it in plain
  * Python).  Little-endian.  A block of bits v1 is at most 368 B, so the N + 1
