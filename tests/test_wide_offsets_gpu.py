@@ -10,8 +10,9 @@ asserted on the device's own contents before the call, block by block) or the se
 (writers: the whole allocation is swept afterwards), so that a bug fails an assertion.
 
 Expected values come from the CPU oracle, tools/bits_ref.py, tools/color_ref.py,
-tools/frame_ref.py, or from the same library call on a compact copy of the same data (the path
-the rest of the suite pins to the oracle); never from the call under test.
+tools/frame_ref.py, tools/scaled_ref.py, tools/window_ref.py, tools/extract_ref.py, or from the
+same library call on a compact copy of the same data (the path the rest of the suite pins to
+the oracle); never from the call under test.  Every comparison is byte equality.
 
 1. Planes (every entry point that takes a dctq_plane), strided views that start 2 GiB (+ 1 MiB
    per geometry) into `big`:
@@ -25,6 +26,20 @@ the rest of the suite pins to the oracle); never from the call under test.
             (compact, a, b, d) of every *_planes entry point
    writers  decode_planes, decode_symbols (4- and 2-byte), decode_bits, the mixed launch, and
             dctq_synth into b and d
+   windows  Plan.decode_bits_window into a-d and the mixed launch: the stored planes are larger
+            than the window in every dimension (three frames with the window on frames 1..,
+            a block origin away from 0 in rows and columns, var_nums of the whole stored
+            plane), so the window's first block, its var_num index and a run's distance from
+            it are all non-zero; expected: the slice of Plan.decode_bits into compact planes
+   scaled   Plan.decode_bits_scaled at 1/2, 1/4 and 1/8 into a-d and the mixed launch: the
+            REDUCED picture is the geometry, so a window row is 18, 36 or 72 blocks (at 1/8 a
+            run of 64 and one of 8).  decode_scaled.hip has a store tail of its own: a and c
+            take its descriptor path with bit 31 set in the offset, b and d its 64-bit path,
+            the mixed launch both in one grid.  In c the 2^31 line and in d the 2^32 line
+            fall between the two pixel rows one lane stores (n = 4), between the two
+            half-waves (n = 2) and between two block rows (n = 1).  Plans q100 and adaptive
+            q50 over blocks of random levels plus noise: the expected picture (scaled_ref on
+            the coefficients bits_decode returns) spans more than 64 levels at every scale
    colour   rgb_to_ycbcr / ycbcr_to_rgb, 4:2:0 and 4:4:4, interleaved and planar, picture and
             planes both wide ("frames": like b, Cb like a; "rows": like d)
    Both aliases of every byte of these cases lie inside the allocation.
@@ -40,15 +55,37 @@ the rest of the suite pins to the oracle); never from the call under test.
    The issue's "2^32 - total" for packed bytes puts the END offset at 2^32, which a uint32
    holds as 0 -- a decreasing offset, outside the format (include/dct_amd.h: non-decreasing
    offsets).  The top-of-range byte stream here ends at 2^32 - 1 (and 2^32 - 2).
+   At the four packed-byte placements also the consumers that take windows,
+   Plan.decode_bits_window, Plan.decode_bits_scaled (2, 4, 8) and bits_window (against
+   tools/extract_ref.py on the host stream: bytes, offsets and var_nums), over two window sets:
+   one with block 101 inside a run of 64 and not as its first block, so the run's first offset
+   is below the crossing and its end above it, and one whose runs all start above it.  The
+   second numbers the same 279 blocks as ONE plane 2 232 pixels wide (the two planes side by
+   side; expected pictures and var_nums concatenated): over the two planes themselves every
+   window set has a run in plane 0, all of whose blocks lie below the crossing.
 3. Stream producers whose totals pass 2^31: dctq_rle_count over ~37 M blocks (4.4 GiB of
    coefficients in `big`), bits_pack over ~8.3 M blocks (offsets only, capacity one byte short
    of a tile boundary past 2^31, the whole stream; then bits_decode and Plan.decode_bits on
    that stream), block_offsets / block_lengths at the API's maximum of 11 671 106 blocks.
    The packed stream is written 4 GiB into `big`: a sign-extended offset lands 2 GiB below,
    in sentinel bytes that are swept.
+   dctq_bits_window_offsets / dctq_bits_window_gather on a window whose OWN payload passes
+   2^31: a stream of 7 981 frames of one block row of 1 021 blocks (8.1 M blocks, 2 GiB + 2.3
+   MiB, tiled from a palette and not packed) and the window of its frames 1.., which drops
+   under 300 KB.  Source (2 GiB + 16 MiB into `big`) and destination (6 GiB + 32 MiB) both
+   have offsets with bit 31 set; the sign-extended alias of every such source offset holds
+   other bytes, that of every destination offset sentinel behind the source's end.  Offsets
+   and var_nums against the source's own, the payload against the source's suffix, a capacity
+   one byte short of a run boundary past 2^31, sweeps around both, the source unchanged; then
+   the window decoder on the last two frames of both streams and the scaled decoder on the
+   source's, against a compact copy's decode_bits and scaled_ref on the palette's coefficients.
 
 Left out, known: rle_emit / encode_planes WRITING symbols past index 2^31 (the symbol buffer
-alone would take 4-9 GiB on top of 4.6 GiB of coefficients)."""
+alone would take 4-9 GiB on top of 4.6 GiB of coefficients).  A window total or a gather
+destination past 2^32 (outside the format: offsets are uint32).  The window consumers of 2.
+with a run in which bit 31 is set in every offset of plane 0 at base 2^31 - k (see there), and
+frame_window / frame_concat / decompress(region=, scale=) past 2 GiB: they are Python over the
+entry points above and torch copies, and a container of that size needs 4 GiB more."""
 import ctypes as C
 import functools
 import os
@@ -64,7 +101,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import bits_ref  # noqa: E402
 import color_ref  # noqa: E402
+import extract_ref  # noqa: E402
 import frame_ref  # noqa: E402
+import scaled_ref  # noqa: E402
+import window_ref  # noqa: E402
 
 MiB, GiB = 1 << 20, 1 << 30
 L30, L31, L32, M32 = 1 << 30, 1 << 31, 1 << 32, (1 << 32) - 1
@@ -114,6 +154,13 @@ def big(T):
 def plan_of(q, ad):
     import dct_amd
     return dct_amd.Plan(q, ad)
+
+
+@functools.lru_cache(maxsize=None)
+def table(q, ad):
+    """The plan's quantization table, as tools/scaled_ref.py takes it."""
+    import dct_amd
+    return dct_amd.debug_tables(q, ad)[3].reshape(8, 8)
 
 
 def gpu(T, a):
@@ -260,6 +307,15 @@ def geo_pixels(name):
     return px
 
 
+LINES = {"a": [L31], "b": [L31, L32], "c": [L31], "d": [L31, L32]}  # the lines a geometry's pixels lie on both sides of
+
+
+def rows_around(g, line):
+    """(the last pixel row of frame 0 that ends below `line`, the first that starts at or past it)."""
+    first = np.arange(g["H"], dtype=np.int64) * g["S"]
+    return int(np.flatnonzero(first + g["W"] - 1 < line).max()), int(np.flatnonzero(first >= line).min())
+
+
 def test_geometries_are_what_the_cases_need():
     for name, g in GEOS.items():
         F, H, W, S, FS = g["F"], g["H"], g["W"], g["S"], g["FS"]
@@ -269,12 +325,30 @@ def test_geometries_are_what_the_cases_need():
         assert g["start"] + span <= BIG and span < 4.5 * GiB
         first = np.array([f * FS + by * 8 * S for f in range(F) for by in range(H // 8)])  # each block row
         last = first + 7 * S + W - 1
-        lines = {"a": [L31], "b": [L31, L32], "c": [L31], "d": [L31, L32]}[name]
-        for line in lines:
+        for line in LINES[name]:
             assert (last < line).any() and (first >= line).any(), (name, line)
         assert (span < M32) == (name in "ac") and span > L31
         if name == "d":
             assert ((first < L32) & (first + 7 * S >= L32)).any(), "no block straddles the 2^32 line"
+        # no alias of any byte leaves the allocation: the aliases depend on F, H, W, S and FS only, so this
+        # holds for every writer into these views, the window and the scaled decoder included
+        it = plane_item(g, geo_pixels(name))
+        for al in it["aliases"].values():
+            assert int(al.min()) >= 0 and int(al.max()) < BIG, name
+        # the scaled decoder writes n = 8 / scale pixel rows a block row, whatever n: single pixel rows
+        # (the unit of n = 1) lie on both sides of every line
+        row = np.array([f * FS + r * S for f in range(F) for r in range(H)])
+        for line in LINES[name]:
+            assert (row + W - 1 < line).any() and (row >= line).any(), (name, line)
+    # where the lines fall among the n-row block rows of the scaled decoder (decode_scaled.hip: lane
+    # (hh, j) stores rows 2 hh and 2 hh + 1 of its block for n = 4, row hh for n = 2)
+    for name, line, pair in (("c", L31, (44, 45)), ("d", L32, (70, 71))):
+        lo, hi = rows_around(GEOS[name], line)
+        assert (lo, hi) == pair, (name, lo, hi)
+        assert lo // 4 == hi // 4 and (lo % 4) // 2 == (hi % 4) // 2 and hi % 2 == 1  # n = 4: one lane's two rows
+        assert lo // 2 == hi // 2 and (lo % 2, hi % 2) == (0, 1)                      # n = 2: across the half-waves
+        assert lo > 0 and hi < GEOS[name]["H"] - 1                                    # n = 1: rows on both sides
+    assert rows_around(GEOS["d"], L31) == (35, 36)  # between two block rows for n = 4 and n = 2
 
 
 def readers_layout(T, big):
@@ -431,6 +505,109 @@ def test_plane_writers(T, dm, big, geo, writer, q, ad):
         if geo == "mixed":
             assert T.equal(outs[0], want[0]), (geo, label, q, ad, "the compact plane")
         check_written(T, big, items, want[len(names) - len(wide):], (geo, label, q, ad))
+
+
+# ---- windows of a stream into wide planes: the window decoder and the scaled decoder -------------------
+def stored_geometry(name, scale=1):
+    """(stored shape, window) of a stream whose window fills geometry `name` at 1 / scale: the
+    window's extent is (F, H scale, W scale); the stored plane has three frames with the window
+    on frames 1.., one block row above and below it, two block columns left and one right of it."""
+    g = GEOS[name]
+    h, w = g["H"] * scale, g["W"] * scale
+    return (3, h + 16, w + 24), ((1, 1 + g["F"]), (8, 8 + h), (16, 16 + w))
+
+
+@functools.lru_cache(maxsize=None)
+def levels_and_noise(shape, seed):
+    """u8 pixels [F, H, W]: every 8 x 8 block has a level of its own in 24..231, plus noise of up to
+    24 either way, so a reduced picture spans the range at every scale (at 1/8 it is the levels)."""
+    rng = np.random.default_rng(seed)
+    f, h, w = shape
+    level = rng.integers(24, 232, (f, h // 8, w // 8)).repeat(8, 1).repeat(8, 2)
+    px = (level + rng.integers(-24, 25, shape)).astype(np.uint8)
+    px.setflags(write=False)
+    return px
+
+
+def window_inputs(T, names, scale, q, ad):
+    """The packed stream of the stored planes around the windows of `names`, made on the compact
+    path: (bytes, offsets, var_nums or None, stored shapes, windows)."""
+    plan = plan_of(q, ad)
+    geo = [stored_geometry(n, scale) for n in names]
+    shapes, windows = [s for s, _ in geo], [w for _, w in geo]
+    for (f, h, w), ((f0, f1), (y0, y1), (x0, x1)) in zip(shapes, windows):  # first, var_first and rel are non-trivial
+        assert 0 < f0 < f1 <= f and 0 < y0 < y1 < h and 0 < x0 < x1 < w
+    planes = [gpu(T, levels_and_noise(s, 40 + k)) for k, s in enumerate(shapes)]
+    vns = [T.zeros(nblocks(p), dtype=T.int32, device="cuda") for p in planes]
+    plan.forward_quant_planes(planes, var_nums=vns)
+    _, boff, by = plan.encode_bits_planes(planes)
+    return by, boff, (vns if ad else None), shapes, windows
+
+
+def wide_outs(T, big, names, mixed):
+    """(outs, items of the wide ones): the views of `names` in `big`; mixed: plane 0 is compact."""
+    outs = [plane_view(big, GEOS[n]) for n in names]
+    if mixed:
+        outs[0] = T.full(geo_pixels(names[0]).shape, SENT, dtype=T.uint8, device="cuda")
+    return outs, [plane_item(GEOS[n], geo_pixels(n)) for n in names[1 if mixed else 0:]]
+
+
+@pytest.mark.parametrize("q,ad", PLANS)
+@pytest.mark.parametrize("geo", list(GEOS) + ["mixed"])
+def test_window_decoder_into_wide_planes(T, dm, big, geo, q, ad):
+    """Plan.decode_bits_window into a-d and the mixed launch: the slice of Plan.decode_bits of the same
+    stream into compact full planes, and not a byte anywhere else in the allocation."""
+    mixed = geo == "mixed"
+    names = tuple(MIXED) if mixed else (geo,)
+    plan = plan_of(q, ad)
+    by, boff, vns, shapes, windows = window_inputs(T, names, 1, q, ad)
+    full = plan.decode_bits(by, boff, shapes=shapes, var_nums=vns)
+    want = [p[f0:f1, y0:y1, x0:x1].contiguous() for p, ((f0, f1), (y0, y1), (x0, x1)) in zip(full, windows)]
+    _state["readers"] = None
+    fill_sentinel(big)
+    outs, items = wide_outs(T, big, names, mixed)
+    got = plan.decode_bits_window(by, boff, shapes, windows, outs=outs, var_nums=vns)
+    assert all(g.data_ptr() == o.data_ptr() for g, o in zip(got, outs))
+    if mixed:
+        assert T.equal(outs[0], want[0]), (geo, q, ad, "the compact plane")
+    check_written(T, big, items, want[len(names) - len(items):], ("decode_bits_window", geo, q, ad))
+
+
+SCALED_PLANS = [(100, 0), (50, 1)]  # the plans whose pictures show where a block landed (tests/test_window_gpu.py)
+
+
+@pytest.mark.parametrize("q,ad", SCALED_PLANS)
+@pytest.mark.parametrize("scale", [2, 4, 8])
+@pytest.mark.parametrize("geo", list(GEOS) + ["mixed"])
+def test_scaled_decoder_into_wide_planes(T, dm, big, geo, scale, q, ad):
+    """Plan.decode_bits_scaled into a-d and the mixed launch, whose reduced pictures are the geometries:
+    tools/scaled_ref.py on the coefficients bits_decode returns, cut to the windows.  a and c take the
+    descriptor path (offsets with bit 31 set), b and d the 64-bit path, the mixed launch both."""
+    mixed = geo == "mixed"
+    names = tuple(MIXED) if mixed else (geo,)
+    plan = plan_of(q, ad)
+    by, boff, vns, shapes, windows = window_inputs(T, names, scale, q, ad)
+    nbs = sorted(set(window_ref.runs(shapes, windows)[:, 1].tolist()))
+    assert nbs == {2: [18], 4: [36], 8: [8, 64]}[scale], nbs
+    coef = dm.bits_decode(by, boff).cpu().numpy()
+    host_vns = [v.cpu().numpy() for v in vns] if ad else None
+    want = scaled_ref.planes(coef, shapes, table(q, ad), scale, ad, host_vns, windows)
+    spans = [int(p.max()) - int(p.min()) for p in want]
+    assert min(spans) > 64, (geo, scale, q, ad, spans)  # a misplaced block shows
+    _state["readers"] = None
+    fill_sentinel(big)
+    outs, items = wide_outs(T, big, names, mixed)
+    for n, o, it in zip(names[len(names) - len(items):], outs[len(names) - len(items):], items):
+        d = dm.plane_desc(o)
+        span = (d.nframes - 1) * d.frame_stride + (d.height - 1) * d.stride + d.width
+        assert (span < M32) == (n in "ac") and span == int(it["off"].max()) + 1, (n, span)
+        for line in LINES[n]:  # pixel rows on both sides of every line the geometry is meant to cross
+            assert (it["off"] < line).any() and (it["off"] >= line).any(), (n, line)
+    got = plan.decode_bits_scaled(by, boff, shapes, scale, windows, outs=outs, var_nums=vns)
+    assert all(g.data_ptr() == o.data_ptr() for g, o in zip(got, outs))
+    if mixed:
+        assert np.array_equal(outs[0].cpu().numpy(), want[0]), (geo, scale, q, ad, "the compact plane")
+    check_written(T, big, items, [gpu(T, w) for w in want[len(names) - len(items):]], ("decode_bits_scaled", geo, scale, q, ad))
 
 
 @pytest.mark.parametrize("kind", ["uniform", "smooth"])
@@ -623,6 +800,55 @@ def placements():
 
 PLACEMENTS = placements()
 
+# Windows for the three consumers that take one (packed bytes only).  The second set numbers the same
+# 279 blocks as ONE plane, the two planes of STREAM_SHAPES side by side: over STREAM_SHAPES itself
+# every window set has a run in plane 0, whose 100 blocks all lie below the crossing.
+STREAM_ROW = [(1, 8, 8 * 279)]
+WINDOW_SETS = {
+    "the crossing inside a run": (STREAM_SHAPES, [((0, 1), (0, 8), (8 * 90, 8 * 100)), ((0, 1), (0, 8), (0, 8 * 70))]),
+    "every run above the crossing": (STREAM_ROW, [((0, 1), (0, 8), (8 * 104, 8 * 188))]),
+}
+
+
+def test_window_sets_are_what_the_cases_need():
+    boff = stream_host()["boff"]
+    crossings = [int(boff[CROSS_BLOCK]) + 1 + par for par in (0, 1)]  # kb of placements(): base + kb is 2^31
+    runs = {name: window_ref.runs(*ws) for name, ws in WINDOW_SETS.items()}
+    inside = [(s0, nb) for s0, nb in runs["the crossing inside a run"].tolist() if s0 < CROSS_BLOCK < s0 + nb]
+    assert len(inside) == 1  # ... and not as the run's first block: its first offset is below, its end above
+    assert all(boff[s0] < kb <= boff[CROSS_BLOCK + 1] <= boff[s0 + nb] for s0, nb in inside for kb in crossings)
+    assert all(s0 > CROSS_BLOCK and boff[s0] > max(crossings) for s0, _ in runs["every run above the crossing"].tolist())
+    for name, r in runs.items():
+        assert 64 in r[:, 1] and r[:, 1].min() < 32, (name, r[:, 1].tolist())
+    assert sum(f * (h // 8) * (w // 8) for f, h, w in STREAM_ROW) == len(stream_blocks())
+
+
+def window_consumers_at_high_offsets(T, dm, src, high, where):
+    """Plan.decode_bits_window, Plan.decode_bits_scaled and bits_window on packed bytes at `high`
+    offsets: slices of the base-0 pictures, tools/scaled_ref.py on the base-0 coefficients, and
+    tools/extract_ref.py on the host stream."""
+    h, want = stream_host(), stream_base0()
+    coef = want["coef"].cpu().numpy()
+    for name, (shapes, windows) in WINDOW_SETS.items():
+        one = len(shapes) == 1
+        vns = [T.cat(want["vns"])] if one else want["vns"]
+        host_vns = [v.cpu().numpy() for v in vns]
+        wb, wo, wv = extract_ref.window_stream(h[1], h["boff"], shapes, windows, host_vns)
+        gb, go, gv = dm.bits_window(src, high, shapes, windows, var_nums=vns)
+        assert np.array_equal(u32(go), wo), (where, name, "bits_window: offsets")
+        assert gb.numel() == len(wb) and np.array_equal(gb.cpu().numpy(), wb), (where, name, "bits_window: bytes")
+        assert all(np.array_equal(g.cpu().numpy(), w) for g, w in zip(gv, wv)), (where, name, "bits_window: var_nums")
+        for q, ad in ((50, 0), (90, 1)):
+            plan, v = plan_of(q, ad), vns if ad else None
+            full = [T.cat(want[q, ad], 2)] if one else want[q, ad]
+            got = plan.decode_bits_window(src, high, shapes, windows, var_nums=v)
+            for g, p, ((f0, f1), (y0, y1), (x0, x1)) in zip(got, full, windows):
+                assert T.equal(g, p[f0:f1, y0:y1, x0:x1]), (where, name, q, ad, "decode_bits_window")
+            for scale in (2, 4, 8):
+                ref = scaled_ref.planes(coef, shapes, table(q, ad), scale, ad, host_vns if ad else None, windows)
+                got = plan.decode_bits_scaled(src, high, shapes, scale, windows, var_nums=v)
+                assert all(np.array_equal(g.cpu().numpy(), r) for g, r in zip(got, ref)), (where, name, q, ad, scale)
+
 
 @pytest.mark.parametrize("where", list(PLACEMENTS))
 def test_stream_consumers_at_high_offsets(T, dm, big, where):
@@ -660,6 +886,8 @@ def test_stream_consumers_at_high_offsets(T, dm, big, where):
         decode = plan_of(q, ad).decode_bits if wd == 1 else plan_of(q, ad).decode_symbols
         got = decode(src, high, shapes=STREAM_SHAPES, var_nums=v)
         assert all(T.equal(a, b) for a, b in zip(got, want[q, ad])), (where, q, ad, decode.__name__)
+    if wd == 1:
+        window_consumers_at_high_offsets(T, dm, src, high, where)
 
 
 # ---- 3. stream producers: running totals that pass 2^31 --------------------------------------------------
@@ -789,6 +1017,113 @@ def test_bits_pack_total_past_2_31(T, dm, big):
     plan, shape = plan_of(50, 0), (1, 8 * rows, 8 * bw)
     got = plan.decode_bits(stream, boff, shapes=[shape])[0]
     assert T.equal(got, plan.decode_planes([coef], shapes=[shape])[0]), "decode_bits != decode_planes(bits_decode)"
+
+
+def as_i32(T, t):
+    """int64 values below 2^32 as the int32 tensor that holds their uint32 bit patterns."""
+    return (((t + L31) & M32) - L31).to(T.int32)
+
+
+def same_bytes(T, a, b):
+    """Two equally long u8 device tensors compared 256 MiB at a time: the first chunk that differs, or None."""
+    flags = [T.equal(a[k:k + CHUNK], b[k:k + CHUNK]) for k in range(0, a.numel(), CHUNK)]
+    return None if all(flags) else flags.index(False)
+
+
+def test_window_payload_past_2_31(T, dm, big):
+    """dctq_bits_window_offsets and dctq_bits_window_gather on a window whose own payload passes 2^31:
+    a stream of the long palette (made by tiling, not by bits_pack) of F frames of one block row of
+    1 021 blocks, and the window of its frames 1..F.  Source and destination both lie in `big`; the
+    sign-extended alias of every source offset holds other bytes, that of every destination offset
+    sentinel.  Then the window and the scaled decoder on the source's last two frames."""
+    _, pby, pboff, pcoef = long_palette()
+    lens, per, bw = np.diff(pboff), int(pboff[-1]), 1021
+    F = -(-((L31 + 2 * 10 ** 6) * PALETTE // per + PALETTE) // bw) + 1
+    while (F * bw) % 64 == 0 or (F * bw) % PALETTE == 0:
+        F += 1
+    n, nw = F * bw, (F - 1) * bw
+    want = expected_offsets(T, lens, n)
+    total, drop = int(want[-1]), int(want[bw])
+    wtotal = total - drop
+    assert L31 + 2 * 10 ** 6 < total < L32 and drop < 300_000 and wtotal > L31 + 10 ** 6 and n < 1 << 26
+    # the layout: [a_lo, a_hi) and [d_lo, d_hi) are where sign-extended source and destination offsets land
+    SRC, DST = 2 * GiB + 16 * MiB, 6 * GiB + 32 * MiB
+    a_lo, a_hi = SRC + L31 - L32, SRC + total - L32
+    d_lo, d_hi = DST + L31 - L32, DST + wtotal - L32
+    assert 0 <= a_lo < a_hi <= SRC and SRC + total <= d_lo < d_hi <= DST and DST + wtotal + 64 <= BIG
+    _state["readers"] = None
+    fill_sentinel(big)
+    period = gpu(T, pby)
+    tile_into(T, big, SRC, period, n // PALETTE, int(pboff[n % PALETTE]))
+    source = big[SRC:SRC + total]
+    other = source[L31:] ^ 0x5A
+    big[a_lo:a_hi].copy_(other)
+    assert bool((big[a_lo:a_hi] != source[L31:]).all()) and equals_tiled(T, source, period) is None
+    soff = as_i32(T, want)
+    assert int(u32(soff[-1:])[0]) == total and int((soff < 0).sum()) > 1021
+    var = T.arange(n, dtype=T.int32, device="cuda")
+
+    shapes, windows = [(F, 8, 8 * bw)], [((1, F), (0, 8), (0, 8 * bw))]
+    wins, wshapes, _ = dm._stored_windows(shapes, windows)
+    assert wshapes == [(F - 1, 8, 8 * bw)]
+    exts = (dm._Extent * 1)(dm._Extent(8 * bw, 8, F - 1))
+    L, s = dm.lib(), C.c_void_p(T.cuda.current_stream().cuda_stream)
+    ws = T.empty(int(L.dctq_bits_window_workspace_bytes(nw)) // 4 + 1, dtype=T.int32, device="cuda")
+    guard = 64
+    woff = T.full((nw + 1 + guard,), -1, dtype=T.int32, device="cuda")
+    wvar = T.full((nw + guard,), -1, dtype=T.int32, device="cuda")
+    vp = (C.c_void_p * 1)(var.data_ptr())
+    rc = L.dctq_bits_window_offsets(soff.data_ptr(), vp, wins, exts, 1, woff.data_ptr(), wvar.data_ptr(), ws.data_ptr(), s)
+    assert rc == 0, L.dctq_error_string(rc)
+    wwant = want[bw:] - drop  # the source's offsets, rebased
+    wrong = (low32(T, woff[:nw + 1]) != wwant).nonzero()
+    assert wrong.numel() == 0, (f"{wrong.numel()} offsets differ, the first at block {int(wrong[0])}",
+                                int(woff[int(wrong[0])]) & M32, int(wwant[int(wrong[0])]))
+    assert T.equal(wvar[:nw], var[bw:]), "win_var_num != var_num from block 1021 on"
+    assert bool((woff[nw + 1:] == -1).all()) and bool((wvar[nw:] == -1).all()), "written past the outputs"
+
+    assert [192, 64] in window_ref.runs([(1, 8, 8 * bw)], [((0, 1), (0, 8), (0, 8 * bw))]).tolist()  # the runs of a row
+    row = int((wwant[::bw] > L31).nonzero()[0]) + 1
+    short = int(wwant[row * bw + 192]) - 1  # one byte short of a run boundary beyond 2^31
+    assert L31 < short < wtotal - 64 * 368
+    suffix = source[drop:]
+    for cap in (short, wtotal):
+        rc = L.dctq_bits_window_gather(source.data_ptr(), soff.data_ptr(), wins, exts, 1, woff.data_ptr(),
+                                       big.data_ptr() + DST, cap, s)
+        assert rc == 0, L.dctq_error_string(rc)
+        bad = same_bytes(T, big[DST:DST + cap], suffix[:cap])
+        assert bad is None, (cap, f"the payload differs from the source's suffix in its 256 MiB chunk {bad}")
+        at = first_dirty(T, big, DST + cap, BIG)
+        assert at is None, (cap, f"byte {at - DST} of the window's stream, at or past the capacity, was written")
+        at = first_dirty(T, big, SRC + total, DST)  # the aliases of the destination offsets lie here
+        assert at is None, (cap, f"a store landed {DST - at} bytes below the window's stream")
+        for lo, hi in ((0, a_lo), (a_hi, SRC)):
+            at = first_dirty(T, big, lo, hi)
+            assert at is None, (cap, f"a store landed at byte {at}, below the source")
+        assert T.equal(big[a_lo:a_hi], other), (cap, "the bytes at the source's aliases were written")
+        assert equals_tiled(T, source, period) is None, (cap, "the source was written")
+
+    # the consumers at offsets the source reached by itself: its last two frames
+    b0 = (F - 2) * bw
+    at0 = int(want[b0])
+    assert at0 > L31
+    compact, coff = source[at0:].clone(), as_i32(T, want[b0:] - at0)
+    last = [((F - 2, F), (0, 8), (0, 8 * bw))]
+    coef = pcoef[np.arange(b0, n) % PALETTE].astype(np.int16)
+    wstream = big[DST:DST + wtotal]
+    wlast = [((F - 3, F - 1), (0, 8), (0, 8 * bw))]
+    for q, ad in ((50, 0), (90, 1)):
+        plan = plan_of(q, ad)
+        ref = plan.decode_bits(compact, coff, shapes=[(2, 8, 8 * bw)], var_nums=[var[b0:]] if ad else None)[0]
+        got = plan.decode_bits_window(source, soff, shapes, last, var_nums=[var] if ad else None)[0]
+        assert T.equal(got, ref), (q, ad, "decode_bits_window on the source != decode_bits of a compact copy")
+        got = plan.decode_bits_window(wstream, woff[:nw + 1], wshapes, wlast, var_nums=[wvar[:nw]] if ad else None)[0]
+        assert T.equal(got, ref), (q, ad, "decode_bits_window on the window's stream != decode_bits of a compact copy")
+        host_vns = [var[b0:].cpu().numpy()] if ad else None
+        for scale in (2, 4, 8):
+            ref = scaled_ref.planes(coef, [(2, 8, 8 * bw)], table(q, ad), scale, ad, host_vns)[0]
+            got = plan.decode_bits_scaled(source, soff, shapes, scale, last, var_nums=[var] if ad else None)[0]
+            assert np.array_equal(got.cpu().numpy(), ref), (q, ad, scale, "decode_bits_scaled != tools/scaled_ref.py")
 
 
 def test_block_offsets_at_the_maximum(T, dm):
