@@ -118,6 +118,10 @@ def _bind(L: C.CDLL, diagnostic: bool) -> C.CDLL:
         "dctq_bits_window_workspace_bytes": ([ll], C.c_size_t),
         "dctq_bits_window_offsets": ([vp, vp, C.POINTER(_Window), C.POINTER(_Extent), i, vp, vp, vp, vp], i),
         "dctq_bits_window_gather": ([vp, vp, C.POINTER(_Window), C.POINTER(_Extent), i, vp, vp, C.c_size_t, vp], i),
+        "dctq_bits_paste_workspace_bytes": ([ll], C.c_size_t),
+        "dctq_bits_paste_offsets": ([vp, vp, vp, vp, C.c_size_t, C.c_size_t, C.POINTER(_Window), C.POINTER(_Extent), i,
+                                     vp, vp, vp, vp], i),
+        "dctq_bits_paste_copy": ([vp, vp, vp, vp, C.POINTER(_Window), C.POINTER(_Extent), i, vp, vp, C.c_size_t, vp], i),
         "dctq_block_lengths": ([vp, ll, i, vp, vp, vp], i),
         "dctq_block_offsets_workspace_bytes": ([ll], C.c_size_t),
         "dctq_block_offsets": ([vp, i, ll, vp, vp, vp], i),
@@ -968,6 +972,60 @@ def bits_window(bytes, offsets, shapes, windows, var_nums=None, stream=None):
     return out, woff, (list(torch.split(wvar, wnbs)) if wvar is not None else None)
 
 
+def bits_paste(bytes, offsets, shapes, windows, patch_bytes, patch_offsets, var_nums=None, patch_var_nums=None,
+               stream=None):
+    """A "bits v1" stream with a window of every plane replaced by another stream's blocks, without
+    decoding: the inverse direction of bits_window (dctq_bits_paste_offsets, dctq_bits_paste_copy;
+    tools/paste_ref.py paste_stream gives the same bytes).  bytes, offsets, shapes, windows and
+    var_nums are as bits_window takes them; patch_bytes / patch_offsets / patch_var_nums are a stream
+    of the windows' own pictures, numbered as bits_window numbers its result, so
+    bits_paste(b, o, shapes, windows, *bits_window(b, o, shapes, windows)[:2]) is (b, o).  Block s of
+    the result is the patch's block when s lies in its plane's window and the base's block s
+    otherwise; lengths are exact differences of offsets.  var_nums and patch_var_nums are both given
+    (one int32 tensor per plane each) or both None.  Returns (bytes' uint8 [total], offsets' int32
+    [N + 1] holding uint32 bit patterns, var_nums': per-plane int32 views of one array, or None).
+    The two payloads together must stay below 2^32 bytes (DctqError before anything is launched:
+    the result's offsets are 32-bit).  Reads the result's payload size back (one sync) and allocates
+    exactly that."""
+    import torch
+    wins, wshapes, nbs = _stored_windows(shapes, windows)
+    wnbs = [_nblocks(s) for s in wshapes]
+    _need_bytes(bytes)
+    _need_byte_offsets(offsets, sum(nbs), bytes)
+    _need_bytes(patch_bytes)
+    _need_byte_offsets(patch_offsets, sum(wnbs), patch_bytes)
+    n, dev = len(wshapes), bytes.device
+    if patch_bytes.device != dev:
+        raise DctqError("bytes and patch_bytes must be on one device")
+    if (var_nums is None) != (patch_var_nums is None):
+        raise DctqError("var_nums and patch_var_nums are both given or both None")
+    if var_nums is not None:
+        for name, vs, counts in (("var_nums", var_nums, nbs), ("patch_var_nums", patch_var_nums, wnbs)):
+            if len(vs) != n:
+                raise DctqError(f"{name} needs one entry per plane ({n}), got {len(vs)}")
+            for k, v in enumerate(vs):
+                _need(v, counts[k], torch.int32, f"{name}[{k}]", dev)
+    if bytes.numel() + patch_bytes.numel() >= 1 << 32:
+        raise DctqError("bits_paste: the two payloads together must stay below 2^32 bytes")
+    exts = (_Extent * n)(*[_Extent(w, h, f) for f, h, w in wshapes])
+    total_blocks = sum(nbs)
+    L, s = lib(), _stream_ptr(stream)
+    ws = _workspace(L.dctq_bits_paste_workspace_bytes, total_blocks, dev)
+    ooff = torch.empty(total_blocks + 1, dtype=torch.int32, device=dev)
+    ovar = torch.empty(total_blocks, dtype=torch.int32, device=dev) if var_nums is not None else None
+    _check(L.dctq_bits_paste_offsets(_ptr(offsets), _ptrs(var_nums), _ptr(patch_offsets), _ptrs(patch_var_nums),
+                                     bytes.numel(), patch_bytes.numel(), wins, exts, n, _ptr(ooff), _ptr(ovar),
+                                     _ptr(ws), s), L)
+    total = _read_back(ooff[total_blocks:], stream)[0]
+    out = torch.empty(total, dtype=torch.uint8, device=dev)
+    if total:
+        # an empty stream has no address: any non-NULL pointer stands for bytes that are never read
+        _check(L.dctq_bits_paste_copy(_ptr(bytes if bytes.numel() else out), _ptr(offsets),
+                                      _ptr(patch_bytes if patch_bytes.numel() else out), _ptr(patch_offsets), wins,
+                                      exts, n, _ptr(ooff), _ptr(out), total, s), L)
+    return out, ooff, (list(torch.split(ovar, nbs)) if ovar is not None else None)
+
+
 def rgb_desc(t, bgr: bool = False):
     """Describe a uint8 device tensor [F, H, W, C] or [H, W, C] (channel axis last in the shape,
     C 3 or 4) as an RGB picture stack, without a copy.  Unit channel stride and a pixel stride of
@@ -1535,6 +1593,11 @@ def decompress(buf, channels: int = 3, planar: bool = False, bgr: bool = False, 
             raise DctqError("decompress: scale together with region is not supported "
                             "(Plan.decode_bits_scaled takes windows)")
     d = frame_unpack(buf, stream=stream)
+    if d["offsets"] is not None and not d["bytes"].numel():
+        # a container of empty blocks (frame_blank): an empty tensor has no address and the decoders
+        # take no NULL, so four bytes of the offsets stand for a payload of which none is read
+        import torch
+        d = dict(d, bytes=d["offsets"].view(torch.uint8)[:4])
     plan = _frame_plan(d["quality"], d["adaptive"], d["bytes"].device)
     crops = d["crops"]
     if scale is not None:
@@ -1651,6 +1714,179 @@ def frame_concat(bufs, stream=None):
             var = torch.cat([d["var_nums"][k] for k in range(nplanes) for d in ds])
     return frame_pack(packed, off, shapes, a["quality"], a["adaptive"], var, a["colour"], stream=stream, crops=a["crops"],
                       length_bytes=max(d["length_bytes"] for d in ds))
+
+
+def _paste_windows(b, p, at, frame):
+    """frame_paste's host rules (tools/paste_ref.py paste_windows): the headers b of the base and p
+    of the patch, `at` and `frame` -> the stored windows of the base, one per plane; DctqError for
+    anything frame_paste refuses."""
+    for key in ("quality", "adaptive", "colour"):
+        if b[key] != p[key]:
+            raise DctqError(f"frame_paste: the patch differs from the container in {key}: {p[key]} != {b[key]}")
+    shapes, pshapes, colour = b["shapes"], p["shapes"], b["colour"]
+    sub = 2 if colour and shapes[1][1:] != shapes[0][1:] else 1
+    if len(pshapes) != len(shapes) or (colour and (2 if pshapes[1][1:] != pshapes[0][1:] else 1) != sub):
+        raise DctqError("frame_paste: the patch differs from the container in its planes or subsampling")
+    crops = b["crops"] or [(0, 0)] * len(shapes)
+    pcrops = p["crops"] or [(0, 0)] * len(shapes)
+    npic = 1 if colour else len(shapes)
+    m = 8 * sub
+    true = [(h - pb, w - pr) for (_, h, w), (pb, pr) in zip(shapes, crops)][:npic]
+    try:
+        single = not hasattr(at[0], "__len__")
+    except (TypeError, IndexError):
+        raise DctqError("at must be (y, x)" + ("" if colour else ", or a list of one per plane")) from None
+    if single:
+        if len(set(true)) != 1:
+            raise DctqError("the planes differ in size: at must be a list of one (y, x) per plane")
+        ats = [_pair(at, "at")] * npic
+    elif colour or len(at) != npic:
+        raise DctqError("at must be (y, x)" + ("" if colour else f", or a list of {npic} of them"))
+    else:
+        ats = [_pair(a, "at") for a in at]
+    frame = int(frame)
+    windows = []
+    for k, ((y, x), (th, tw)) in enumerate(zip(ats, true)):
+        if y < 0 or x < 0 or y % m or x % m:
+            raise DctqError(f"frame_paste: at must be non-negative multiples of {m} (a stream cannot begin inside a "
+                            f"block), got {(y, x)}")
+        pf, ph, pw = pshapes[k]
+        if frame < 0 or frame + pf > shapes[k][0]:
+            raise DctqError(f"frame_paste: frames {(frame, frame + pf)} leave the {shapes[k][0]} frames")
+        for axis, a0, stored, pad, t in (("rows", y, ph, pcrops[k][0], th), ("columns", x, pw, pcrops[k][1], tw)):
+            if not ((pad == 0 and a0 + stored <= t) or a0 + stored - pad == t):
+                raise DctqError(f"frame_paste: plane {k}: the patch's {axis} {(a0, a0 + stored - pad)} must end inside "
+                                f"the true picture of {t} without a crop, or exactly on its edge: anything else would "
+                                "write replicated edge pixels over real ones")
+        windows.append(((frame, frame + pf), (y, y + ph), (x, x + pw)))
+    if colour:
+        (fr, (ya, yb), (xa, xb)) = windows[0]
+        windows += [(fr, (ya // sub, yb // sub), (xa // sub, xb // sub))] * 2
+    return windows
+
+
+def frame_paste(buf, patch, at=(0, 0), frame: int = 0, stream=None):
+    """The container buf with the container patch written in, without decoding either: the inverse
+    of frame_window (frame_unpack of both, bits_paste, frame_pack; tools/paste_ref.py frame_paste
+    gives the same bytes).  at=(y, x): where the patch's first pixel goes, in pixels of buf's TRUE
+    picture (plain planes: one pair when every plane has one true size, or a list of one per
+    plane); frame: the first frame it replaces.  The result has buf's geometry and crops;
+    length_bytes is chosen from the result's own blocks.  Refused with DctqError before anything
+    is launched: a patch that differs in quality, adaptive, colour, the number of planes or the
+    subsampling; at that is not multiples of m (8; 16 for a 4:2:0 picture); frame + the patch's
+    frames beyond buf's; and, on each axis, a patch that neither has no crop and ends inside the
+    true picture, nor has its TRUE extent end exactly on the true picture's edge (then its padded
+    rows and columns are exactly what compress of the edited picture writes there) -- anything
+    else would write replicated edge pixels over real ones.
+    frame_paste(b, frame_window(b, region, frames), at=the region's start, frame=frames[0]) is b
+    byte for byte, frame_paste(compress(x), compress(p), at, f) is compress(x with p written in),
+    and decompress of the result is decompress(buf) with decompress(patch) written in: the blocks
+    that are not replaced keep their bytes, so nothing goes through a second generation."""
+    buf, hb = _frame_open(buf, stream)
+    patch, hp = _frame_open(patch, stream)
+    if patch.device != buf.device:
+        raise DctqError("frame_paste: the containers must be on one device")
+    windows = _paste_windows(hb, hp, at, frame)
+    d, p = _frame_parts(buf, hb, stream), _frame_parts(patch, hp, stream)
+    packed, off, var = bits_paste(d["bytes"], d["offsets"], d["shapes"], windows, p["bytes"], p["offsets"],
+                                  d["var_nums"], p["var_nums"], stream=stream)
+    return frame_pack(packed, off, d["shapes"], d["quality"], d["adaptive"], var, d["colour"], stream=stream,
+                      crops=d["crops"])
+
+
+def frame_blank(shapes, quality, adaptive=False, colour=False, crops=None, device="cuda", stream=None):
+    """A container of the stored shapes [(F, H, W)] whose every block has length 0 and, for an
+    adaptive plan, var_num 0 (tools/paste_ref.py frame_blank gives the same bytes).  An empty block
+    is valid bits v1 and decodes as zero coefficients, so the container decompresses to flat
+    mid-grey; it is what frame_tile pastes into.  quality, adaptive, colour and crops as frame_pack."""
+    import torch
+    shapes = _shapes3(shapes)
+    n = _frame_geometry(shapes, colour)
+    with _on_stream(stream):
+        off = torch.zeros(n + 1, dtype=torch.int32, device=device)
+        var = torch.zeros(n, dtype=torch.int32, device=device) if adaptive else None
+        packed = torch.empty(0, dtype=torch.uint8, device=device)
+    return frame_pack(packed, off, shapes, quality, adaptive, var, colour, stream=stream, crops=crops)
+
+
+def _tile_layout(hs):
+    """frame_tile's host rules (tools/paste_ref.py tile_layout): the grid of headers -> (shapes,
+    crops, ats): the joined container's stored shapes and crops, and each tile's `at`."""
+    rows, cols = len(hs), len(hs[0]) if hs else 0
+    if rows < 1 or cols < 1 or any(len(row) != cols for row in hs):
+        raise DctqError("frame_tile: a grid of one or more rows of equal length")
+    a = hs[0][0]
+    colour, n = a["colour"], len(a["shapes"])
+    sub = 2 if colour and a["shapes"][1][1:] != a["shapes"][0][1:] else 1
+    for row in hs:
+        for h in row:
+            for key in ("quality", "adaptive", "colour"):
+                if h[key] != a[key]:
+                    raise DctqError(f"frame_tile: the containers differ in {key}: {h[key]} != {a[key]}")
+            if (len(h["shapes"]) != n or (colour and (2 if h["shapes"][1][1:] != h["shapes"][0][1:] else 1) != sub)
+                    or [s[0] for s in h["shapes"]] != [s[0] for s in a["shapes"]]):
+                raise DctqError("frame_tile: the containers differ in their planes, subsampling or frames")
+    npic = 1 if colour else n
+
+    def true(h, k):
+        (_, hh, ww), (pb, pr) = h["shapes"][k], (h["crops"] or [(0, 0)] * n)[k]
+        return hh - pb, ww - pr, pb, pr
+
+    shapes, crops, ys, xs = [], [], [], []
+    for k in range(npic):
+        for r, row in enumerate(hs):
+            if len({true(h, k)[0] for h in row}) != 1:
+                raise DctqError(f"frame_tile: plane {k}: true heights differ along row {r}")
+            if r < rows - 1 and any(true(h, k)[2] for h in row):
+                raise DctqError("frame_tile: only the last row may carry a bottom crop")
+        for c in range(cols):
+            col = [row[c] for row in hs]
+            if len({true(h, k)[1] for h in col}) != 1:
+                raise DctqError(f"frame_tile: plane {k}: true widths differ along column {c}")
+            if c < cols - 1 and any(true(h, k)[3] for h in col):
+                raise DctqError("frame_tile: only the last column may carry a right crop")
+        y, x = [0], [0]
+        for row in hs:
+            y.append(y[-1] + true(row[0], k)[0])
+        for h in hs[0]:
+            x.append(x[-1] + true(h, k)[1])
+        pb, pr = true(hs[-1][0], k)[2], true(hs[0][-1], k)[3]
+        ys.append(y)
+        xs.append(x)
+        shapes.append((a["shapes"][k][0], y[-1] + pb, x[-1] + pr))
+        crops.append((pb, pr))
+    if colour:
+        f, hh, ww = shapes[0]
+        shapes += [(f, hh // sub, ww // sub)] * 2
+        crops += [(0, 0), (0, 0)]
+    ats = [[(ys[0][r], xs[0][c]) if colour else [(ys[k][r], xs[k][c]) for k in range(n)] for c in range(cols)]
+           for r in range(rows)]
+    return shapes, crops, ats
+
+
+def frame_tile(grid, stream=None):
+    """A list of rows of containers joined spatially into one container, without decoding: the
+    spatial counterpart of frame_concat (tools/paste_ref.py frame_tile gives the same bytes).  All
+    containers must agree in quality, adaptive, colour, the number of planes, the subsampling and
+    the frames; true heights must be equal along a row and true widths along a column; only the
+    last row and the last column may carry a crop (every other tile is whole blocks of m: 8; 16
+    for a 4:2:0 picture); else DctqError before anything is launched.  frame_tile of the tiles'
+    compress is byte for byte compress of the joined picture, so band shards (dct_amd/shard.py)
+    that each compress their band become one container with no coefficients or pixels moved.
+    Built as frame_blank plus one frame_paste per tile: K tiles are K passes over the payload built
+    so far (each a copy of what the earlier ones wrote), which is simple and not the fastest way
+    to join many tiles."""
+    opened = [[_frame_open(b, stream) for b in row] for row in grid]
+    shapes, crops, ats = _tile_layout([[h for _, h in row] for row in opened])
+    a = opened[0][0][1]
+    if any(b.device != opened[0][0][0].device for row in opened for b, _ in row):
+        raise DctqError("frame_tile: the containers must be on one device")
+    out = frame_blank(shapes, a["quality"], a["adaptive"], a["colour"], crops, device=opened[0][0][0].device,
+                      stream=stream)
+    for row, at_row in zip(opened, ats):
+        for (b, _), at in zip(row, at_row):
+            out = frame_paste(out, b, at=at, frame=0, stream=stream)
+    return out
 
 
 def symbol_bytes(quality: int, adaptive: bool = False) -> int:

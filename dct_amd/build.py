@@ -27,7 +27,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdct_amd.so")
 DIAG_LIB = os.path.join(HERE, "libdct_amd_diag.so")
 DIAG_SOURCES = ["diag.hip", "fdct8_diag.hip"]
-SOURCES = ["api.hip", "plan_tables.hip", "isolation.hip", "legacy.hip", "fdct8.hip", "fdct8_aux.hip", "f64_pair.hip", "rle.hip", "roundtrip.hip", "encode.hip", "huffman.hip", "decode.hip", "decode_symbols.hip", "distortion.hip", "bits.hip", "decode_bits.hip", "decode_window.hip", "decode_scaled.hip", "extract.hip", "color.hip", "color_pad.hip", "frame.hip"]
+SOURCES = ["api.hip", "plan_tables.hip", "isolation.hip", "legacy.hip", "fdct8.hip", "fdct8_aux.hip", "f64_pair.hip", "rle.hip", "roundtrip.hip", "encode.hip", "huffman.hip", "decode.hip", "decode_symbols.hip", "distortion.hip", "bits.hip", "decode_bits.hip", "decode_window.hip", "decode_scaled.hip", "extract.hip", "paste.hip", "color.hip", "color_pad.hip", "frame.hip"]
 HEADERS = ["dctq_internal.h", "plan.h", "dctq_diag.h", "fdct8_bound.h", "idct8_bound.h", "host_tables.h", "aan_f64.h", "fdct8_core.h", "pair_core.h", "inverse_core.h", "scan_core.h", "zigzag.h", "rle_decode_core.h", "decode_core.h", "bits_core.h", "tile_decode_core.h", "window_core.h", "color_core.h"]
 ARCH = "gfx950"
 

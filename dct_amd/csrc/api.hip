@@ -501,6 +501,72 @@ int dctq_bits_window_gather(const uint8_t *bytes, const uint32_t *offsets, const
     return DCTQ_OK;
 }
 
+// The stream paste's geometry: the extraction's windows, plus each stored plane's first block
+// (first[k]; first[nplanes..] the stored blocks in all, < 2^26 after window_set).
+static int paste_window_set(const dctq_window *win, const dctq_extent *ext, int nplanes, dctq::WindowSet *ws,
+                            uint32_t *first) {
+    if (int rc = extent_window_set(win, ext, nplanes, ws)) return rc;
+    uint32_t next = 0;
+    for (int k = 0; k <= dctq::kMaxPlanes; ++k) {
+        first[k] = next;
+        if (k < nplanes) next += (uint32_t)((long long)(win[k].width / 8) * (win[k].height / 8) * win[k].nframes);
+    }
+    return DCTQ_OK;
+}
+
+size_t dctq_bits_paste_workspace_bytes(long long stored_blocks) { return scan_workspace_bytes(stored_blocks); }
+
+int dctq_bits_paste_offsets(const uint32_t *offsets, const int32_t *const *var_num, const uint32_t *patch_offsets,
+                            const int32_t *const *patch_var_num, size_t payload_bytes, size_t patch_payload_bytes,
+                            const dctq_window *win, const dctq_extent *ext, int nplanes, uint32_t *out_offsets,
+                            int32_t *out_var_num, void *workspace, void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryBitsPasteOffsets);
+    dctq::WindowSet ws;
+    uint32_t first[dctq::kMaxPlanes + 1];
+    if (int rc = paste_window_set(win, ext, nplanes, &ws, first)) return rc;
+    // the result holds at most both payloads, and its offsets are 32-bit
+    if ((unsigned long long)payload_bytes >= (1ull << 32) || (unsigned long long)patch_payload_bytes >= (1ull << 32) ||
+        (unsigned long long)payload_bytes + (unsigned long long)patch_payload_bytes >= (1ull << 32))
+        return fail(DCTQ_EINVAL, "paste: payload_bytes + patch_payload_bytes must stay below 2^32");
+    if (!offsets || !patch_offsets || !out_offsets) return fail(DCTQ_EINVAL, "offsets/patch_offsets/out_offsets is NULL");
+    if (misaligned(offsets, 4) || misaligned(patch_offsets, 4) || misaligned(out_offsets, 4))
+        return fail(DCTQ_EINVAL, "offsets, patch_offsets and out_offsets must be 4-byte aligned");
+    if (!var_num != !patch_var_num) return fail(DCTQ_EINVAL, "paste: var_num and patch_var_num are both given or both NULL");
+    if (var_num) {
+        if (!out_var_num || misaligned(out_var_num, 4))
+            return fail(DCTQ_EINVAL, "var_num given but out_var_num is NULL or not 4-byte aligned");
+        for (int k = 0; k < nplanes; ++k) {
+            if (!var_num[k] || misaligned(var_num[k], 4) || !patch_var_num[k] || misaligned(patch_var_num[k], 4))
+                return fail(DCTQ_EINVAL, "var_num given but var_num[k] or patch_var_num[k] is NULL or not 4-byte aligned");
+            ws.var[k] = var_num[k];
+        }
+    }
+    if (int rc = check_workspace(workspace)) return rc;
+    HIPCHK(dctq::launch_bits_paste_offsets(ws, first, offsets, patch_offsets, var_num ? patch_var_num : nullptr,
+                                           out_offsets, var_num ? out_var_num : nullptr, workspace,
+                                           (hipStream_t)stream, device_cus()),
+           "bits_paste_offsets launch");
+    return DCTQ_OK;
+}
+
+int dctq_bits_paste_copy(const uint8_t *bytes, const uint32_t *offsets, const uint8_t *patch_bytes,
+                         const uint32_t *patch_offsets, const dctq_window *win, const dctq_extent *ext, int nplanes,
+                         const uint32_t *out_offsets, uint8_t *out_bytes, size_t capacity, void *stream) {
+    DCTQ_LAUNCH(stream, dctq::kEntryBitsPasteCopy);
+    dctq::WindowSet ws;
+    uint32_t first[dctq::kMaxPlanes + 1];
+    if (int rc = paste_window_set(win, ext, nplanes, &ws, first)) return rc;
+    if (!bytes || !offsets || !patch_bytes || !patch_offsets || !out_offsets || !out_bytes)
+        return fail(DCTQ_EINVAL, "bytes/offsets/patch_bytes/patch_offsets/out_offsets/out_bytes is NULL");
+    if (misaligned(offsets, 4) || misaligned(patch_offsets, 4) || misaligned(out_offsets, 4))
+        return fail(DCTQ_EINVAL, "offsets, patch_offsets and out_offsets must be 4-byte aligned");
+    if (!capacity) return DCTQ_OK;
+    HIPCHK(dctq::launch_bits_paste_copy(ws, first, bytes, offsets, patch_bytes, patch_offsets, out_offsets, out_bytes,
+                                        (unsigned long long)capacity, (hipStream_t)stream, device_cus()),
+           "bits_paste_copy launch");
+    return DCTQ_OK;
+}
+
 int dctq_synth(uint64_t seed, int kind, const dctq_plane *dst, void *stream) {
     DCTQ_LAUNCH(stream, dctq::kEntrySynth);
     if (!dst || !dst->pixels) return fail(DCTQ_EINVAL, "dst is NULL");

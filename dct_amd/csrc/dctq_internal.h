@@ -38,7 +38,7 @@ class RandIsolation {
 // an entry point on a stream, so that call is isolated as above; every later call
 // of the thread with the same (device, stream, entry point) takes no lock and
 // touches no global state (the reference API is reentrant and keeps
-// no mutable global state).  `entry` names the entry point: one bit of a 32-bit mask each.
+// no mutable global state).  `entry` names the entry point: one bit of a 64-bit mask each.
 enum Entry : int {
     kEntryForwardQuantPlanes,
     kEntryRoundTripPlanes,
@@ -71,8 +71,10 @@ enum Entry : int {
     kEntryDecodeBitsWindowScaledPlanes,
     kEntryBitsWindowOffsets,
     kEntryBitsWindowGather,
+    kEntryBitsPasteOffsets,
+    kEntryBitsPasteCopy,
 };
-static_assert(kEntryBitsWindowGather < 32, "LaunchIsolation keeps one bit per entry point in a uint32_t");
+static_assert(kEntryBitsPasteCopy < 64, "LaunchIsolation keeps one bit per entry point in a uint64_t");
 class LaunchIsolation {
   public:
     LaunchIsolation(const void *stream, Entry entry);
@@ -446,6 +448,18 @@ hipError_t launch_bits_window_offsets(const WindowSet &ws, const uint32_t *offse
 hipError_t launch_bits_window_gather(const WindowSet &ws, const uint8_t *bytes, const uint32_t *offsets,
                                      const uint32_t *win_offsets, uint8_t *win_bytes, unsigned long long capacity,
                                      hipStream_t stream, int num_cus);
+// a window of a packed stream replaced by a patch stream's blocks (paste.hip): ws as for the extraction
+// (ws.var the base's stored planes' var_num when out_var is set, patch_var then the patch's per plane),
+// first[k] each stored plane's first block and first[n..kMaxPlanes] the stored blocks in all; the
+// result's offsets (and var_num), then its bytes below `capacity`; wsp: rle_workspace_bytes(stored blocks)
+hipError_t launch_bits_paste_offsets(const WindowSet &ws, const uint32_t *first, const uint32_t *offsets,
+                                     const uint32_t *patch_offsets, const int32_t *const *patch_var,
+                                     uint32_t *out_offsets, int32_t *out_var, void *wsp, hipStream_t stream,
+                                     int num_cus);
+hipError_t launch_bits_paste_copy(const WindowSet &ws, const uint32_t *first, const uint8_t *bytes,
+                                  const uint32_t *offsets, const uint8_t *patch_bytes, const uint32_t *patch_offsets,
+                                  const uint32_t *out_offsets, uint8_t *out_bytes, unsigned long long capacity,
+                                  hipStream_t stream, int num_cus);
 // byte offsets of a packed stream <-> one or two bytes of length per block (frame.hip); ws: rle_workspace_bytes(nblk)
 hipError_t launch_block_lengths(const uint32_t *offsets, long long nblk, int length_bytes, void *lengths,
                                 uint32_t *max_length, hipStream_t stream, int num_cus);

@@ -41,7 +41,7 @@ struct SeenKey {
     int device;
     const void *stream;
     unsigned long long id;  // hipStreamGetId: a re-created stream at a reused handle has another id
-    uint32_t entries;       // bit e: entry point e already called by this thread on (device, stream)
+    uint64_t entries;       // bit e: entry point e already called by this thread on (device, stream)
 };
 thread_local std::vector<SeenKey> t_seen;
 constexpr unsigned long long kNoId = ~0ull;
@@ -79,7 +79,7 @@ static unsigned long long stream_id(const void *stream) {
 }
 
 LaunchIsolation::LaunchIsolation(const void *stream, Entry entry) {
-    const uint32_t bit = 1u << entry;
+    const uint64_t bit = 1ull << entry;
     int dev = -1;
     unsigned long long id = kNoId;
     if (runtime_started() && hipGetDevice(&dev) == hipSuccess) {
@@ -94,7 +94,7 @@ LaunchIsolation::LaunchIsolation(const void *stream, Entry entry) {
     if (id == kNoId) id = stream_id(stream);
     for (SeenKey &k : t_seen)
         if (k.device == dev && k.stream == stream) {
-            if (k.id != id) k = SeenKey{dev, stream, id, 0u};  // the handle now names another stream
+            if (k.id != id) k = SeenKey{dev, stream, id, 0ull};  // the handle now names another stream
             k.entries |= bit;
             return;
         }

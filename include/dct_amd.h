@@ -445,6 +445,56 @@ int dctq_bits_window_gather(const uint8_t *bytes, const uint32_t *offsets, const
                             const dctq_extent *ext, int nplanes, const uint32_t *win_offsets, uint8_t *win_bytes,
                             size_t capacity, void *stream);
 
+/* A window of a packed stream REPLACED by another packed stream's blocks, without
+ * decoding: the inverse direction of the two calls above.  The base stream (bytes,
+ * offsets, var_num) holds the N blocks of nplanes stored planes; win[k] and ext[k]
+ * describe plane k's window exactly as above; the patch stream (patch_bytes,
+ * patch_offsets, patch_var_num) holds the N' blocks of the windows' own pictures, in
+ * the numbering dctq_bits_window_offsets produces.  The result has the stored
+ * geometry: for its block s (s_k inside plane k)
+ *   out block s = patch block d  when s lies in its plane's window, d the block's
+ *                                number in the window's own picture (d_k inside it),
+ *               = base block s   otherwise;
+ *   out_offsets[s + 1] - out_offsets[s] = that block's length (mod 2^32, exact: no
+ *                                clamp to 368),  out_offsets[0] = 0
+ *   out_bytes[out_offsets[s] .. out_offsets[s + 1]) = that block's bytes
+ *   out_var_num[s] = patch_var_num[k][d_k] or var_num[k][s_k]
+ * for any bytes and any non-decreasing offsets (tools/paste_ref.py states it in
+ * plain numpy).  payload_bytes and patch_payload_bytes are the caller's statement of
+ * the two streams' sizes, offsets[N] - offsets[0] and patch_offsets[N'] -
+ * patch_offsets[0]: the result is at most their sum, which must stay below 2^32
+ * because the result's offsets are 32-bit.
+ * dctq_bits_paste_offsets writes out_offsets[0 .. N] (out_offsets[N] is the result's
+ * payload size) and, when var_num is not NULL, out_var_num[0 .. N) (one array, the
+ * planes concatenated; var_num[k] is the whole stored plane's, patch_var_num[k] the
+ * whole window's).  var_num and patch_var_num are both given or both NULL.
+ * workspace: device memory of dctq_bits_paste_workspace_bytes(N) bytes, 4-byte
+ * aligned.
+ * dctq_bits_paste_copy writes the bytes, given the out_offsets of the first call: one
+ * wave per tile of 64 result blocks, whose bytes are contiguous; the tile is split
+ * where the source changes or stops being consecutive, and each piece is one byte
+ * copy as in dctq_bits_window_gather.  Nothing outside the source blocks' bytes is
+ * read, and nothing outside [out_offsets[t0], min(out_offsets[t0 + nb], capacity))
+ * of a tile is written: no byte at or past out_bytes + capacity, so a short buffer
+ * gets the payload's first `capacity` bytes.  bytes, patch_bytes and out_bytes may
+ * sit at any alignment; every offsets and var_num array is 4-byte aligned.  A stored
+ * plane or a window narrower than 64 blocks gives many short pieces per tile: correct,
+ * not fast.  The first call reads about 8 B and writes 4 B per block (+ 8 B adaptive),
+ * the second reads about 16 B per block and reads and writes the result's payload.
+ * DCTQ_EINVAL, before any launch and before a device is looked at: everything
+ * dctq_bits_window_offsets refuses in win, ext and nplanes (through the same check);
+ * then payload_bytes + patch_payload_bytes >= 2^32; then a NULL or misaligned
+ * pointer, var_num without patch_var_num or the reverse, or var_num without
+ * out_var_num.  Asynchronous on stream; allocate nothing. */
+size_t dctq_bits_paste_workspace_bytes(long long stored_blocks);
+int dctq_bits_paste_offsets(const uint32_t *offsets, const int32_t *const *var_num, const uint32_t *patch_offsets,
+                            const int32_t *const *patch_var_num, size_t payload_bytes, size_t patch_payload_bytes,
+                            const dctq_window *win, const dctq_extent *ext, int nplanes, uint32_t *out_offsets,
+                            int32_t *out_var_num, void *workspace, void *stream);
+int dctq_bits_paste_copy(const uint8_t *bytes, const uint32_t *offsets, const uint8_t *patch_bytes,
+                         const uint32_t *patch_offsets, const dctq_window *win, const dctq_extent *ext, int nplanes,
+                         const uint32_t *out_offsets, uint8_t *out_bytes, size_t capacity, void *stream);
+
 /* Self-contained container, format "frame v1": everything a decoder of a "bits
  * v1" stream needs, in one byte buffer (tools/frame_ref.py states it in plain
  * Python).  Little-endian.  A block of bits v1 is at most 368 B, so the N + 1
